@@ -13,7 +13,16 @@ datasets/transforms.py:147-161), fp32, iters=16, max_disp=320, random-init weigh
 processes its own video (weak scaling; no data-path collective); the only collective is the single
 all_reduce of the [3,12] metric tensor after the timed frames, inside the timed region.
 
-Prints ONE JSON line on rank 0 (see README / task contract), including
+A plain run (``--gpus 1 --steps K --warmup W``) does only what the headline needs: set up, prime + pre-warm + W warm-up
+frames, the K timed frames, ``--dump-outputs DIR`` if given, and ONE JSON line on rank 0 (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds of one timed frame, config, epe_vs_synthetic_gt).
+
+``--dump-outputs DIR`` writes what the timed path returned for its LAST timed frame as float32 ``DIR/<name>.npy``:
+pred_disp (the disparity FrameRunner.step returns) and, with motion, Ts (the SE3 field of FrameRunner.last); ranks > 0
+add a ``_rank<r>`` suffix.  At most 64 MB in all: an array over its share is replaced by a fixed, seeded sample of its
+elements.  Inputs and weights are deterministic, so two builds can be compared output for output.
+
+``--full`` (off by default) adds the secondary measurements after the timed region, each in the JSON line:
   roofline     -- MFMA roofline of the dominant kernel family (conv_bf16_kernel, the split-bf16 convolutions of
                   RAFT3D): MFMA FLOPs ISSUED (3 bf16 MFMAs per product) by its launches of one frame /
                   their summed duration measured with HIP events on the launch stream, vs the 2.5 PFLOP/s dense
@@ -21,8 +30,10 @@ Prints ONE JSON line on rank 0 (see README / task contract), including
                   vs the 157.3 TFLOP/s fp32 matrix peak, are reported beside it;
                   roofline.traffic is measured by this run itself (two rocprofv3 --pmc child passes of this script,
                   FETCH_SIZE and WRITE_SIZE separately; --no-pmc-traffic quotes the committed capture instead);
+  fp32_exact_fps -- the same frame with every convolution on the exact-fp32 kernels;
   fps_two_videos_per_gpu -- two independent videos resident on the GPU (two frame graphs on two streams): throughput
-                  headroom reported beside the one-video-per-GPU headline;
+                  headroom reported beside the one-video-per-GPU headline (fps_two_videos_batched: the same two videos
+                  as one B = 2 batch);
   cpu_baseline -- the CPU oracle (port of the reference's PyTorch-CPU path) timed on this host's
                   cores: BASELINE.json configs[0] (512x256, 2 frames, stereo only) and ONE measured
                   steady-state frame of the benchmarked configuration (no scaling).
@@ -51,6 +62,7 @@ PAD_H, PAD_W = 576, 960
 FP32_MATRIX_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md chip-level parameters
 BF16_MATRIX_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA (same table)
 HBM_PEAK_GBS = 8000.0  # HBM3E (same table)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files of the job together
 
 
 def _hbm_specs():
@@ -106,6 +118,11 @@ def parse():
                     help="untimed steady-state frames run before the W warm-up steps so that the GPU clocks and "
                          "the captured graph are in steady state (reported in config.prewarm_frames)")
     ap.add_argument("--iters", type=int, default=16)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the secondary measurements (roofline + PMC traffic passes, "
+                         "fp32-exact pass, two-video passes, CPU baseline) and report them in the JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the timed path returned for its last timed frame to DIR/<name>.npy (float32)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
@@ -120,14 +137,14 @@ def parse():
                          "fp16's range applies there (|x| > 65504 -> inf; HITNet's channels carry raw disparities): dev modes")
     ap.add_argument("--stereo-only", action="store_true")
     ap.add_argument("--fp32-steps", type=int, default=30,
-                    help="after the timed region (rank 0, N = 1, split precision only): time this many steady-state frames "
+                    help="--full, after the timed region (rank 0, N = 1, split precision only): time this many steady-state frames "
                          "with EVERY convolution on the exact-fp32 kernels and report them as fp32_exact_fps (0 = skip)")
     ap.add_argument("--two-video-steps", type=int, default=60,
-                    help="after the timed region (rank 0, N = 1): frames per video of a pass with TWO independent videos "
+                    help="--full, after the timed region (rank 0, N = 1): frames per video of a pass with TWO independent videos "
                          "resident on the GPU (two frame graphs on two streams), reported as fps_two_videos_per_gpu -- the "
                          "throughput headroom beside the one-video-per-GPU headline (0 = skip)")
     ap.add_argument("--no-pmc-traffic", dest="pmc_traffic", action="store_false",
-                    help="do not measure roofline.traffic with two rocprofv3 --pmc child passes (N = 1 only, ~40 s); the "
+                    help="--full: do not measure roofline.traffic with two rocprofv3 --pmc child passes (N = 1 only, ~40 s); the "
                          "newest committed capture under profiles/ is quoted instead")
     ap.add_argument("--tune-db", default=None,
                     help="JSON file of tuned launch configurations: loaded if it exists (no tuning launches, e.g. under "
@@ -344,7 +361,7 @@ def pmc_traffic(args, kernel_pattern):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             with tempfile.TemporaryDirectory(dir="/tmp") as td:
                 cmd = [exe, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", td, "-o", "p", "--",
-                       sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--fp32-steps", "0", "--two-video-steps", "0",
+                       sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--fp32-steps", "0", "--two-video-steps", "0",
                        "--no-pmc-traffic", "--serial-streams", "--no-graph", "--steps", "4", "--prewarm", "2", "--warmup", "1",
                        "--precision", args.precision, "--iters", str(args.iters), "--height", str(args.height),
                        "--width", str(args.width)] + (["--stereo-only"] if args.stereo_only else [])
@@ -436,6 +453,20 @@ def cpu_baseline_subprocess(args, timeout=420):
                     sample=f"CPU oracle sample did not finish within {timeout} s")
     except Exception as e:  # pragma: no cover
         return dict(value=None, unit="frames/s", cores=args.cpu_threads, kind="port", sample=f"failed: {e!r}")
+
+
+def dump_outputs(outdir, arrays, suffix="", parts=1):
+    """--dump-outputs: ``arrays`` (name -> numpy array) as float32 ``outdir/<name><suffix>.npy``.  The job's files stay
+    within DUMP_LIMIT_BYTES: each of its ``parts`` arrays gets an equal share, and one larger than its share is replaced
+    by a fixed, seeded sample of its elements (flattened, in index order)."""
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, parts)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + suffix + ".npy"), a)
 
 
 def timed_region(step, frame_fn, steps, update_metric, metric_row, device, use_dist):
@@ -593,11 +624,21 @@ def main():
                  lambda d, g: warm.update_disparity_device(d, g, (raw_h, raw_w)), warm.row, device, use_dist)
     log(f"{args.prewarm} pre-warm + {max(args.warmup, 1)} warm-up frames done")
     seqm = metrics.SequenceMetrics(metas[0][0], device)
+    timed_step, last = step, {}
+    if args.dump_outputs:  # keep a handle on what the last timed frame returned (no copy inside the timed region)
+        def timed_step(l, r):
+            last["pred_disp"] = step(l, r)
+            return last["pred_disp"]
 
-    dt, red = timed_region(step, lambda i: frame(1 + args.prewarm + args.warmup + i), args.steps,
+    dt, red = timed_region(timed_step, lambda i: frame(1 + args.prewarm + args.warmup + i), args.steps,
                            lambda d, g: seqm.update_disparity_device(d, g, (raw_h, raw_w)), seqm.row, device, use_dist)
 
     log(f"timed region done: {dt:.3f} s")
+    if args.dump_outputs:  # before anything else runs on the GPU: the graph's output buffers are reused by the next frame
+        outs = {k: v.detach().float().cpu().numpy() for k, v in last.items()}
+        outs.update({k: v.detach().float().cpu().numpy() for k, v in runner.last.items()})
+        dump_outputs(args.dump_outputs, outs, "" if rank == 0 else f"_rank{rank}", parts=world * len(outs))
+        log(f"outputs of the last timed frame written to {args.dump_outputs}: {sorted(outs)}")
     tuned_for_headline = len(_ops_tune.AUTOTUNE_LOG)  # layer signatures of THIS workload that the shipped db did not know (timed in frames 0-1)
     # every rank reports in: (rank, local GPU index, frames it timed) gathered over RCCL -> ranks_seen in the JSON line
     ranks_seen = [[rank, local, args.steps]]
@@ -621,7 +662,7 @@ def main():
     fp32_fps = None
     two_fps = None
     batched_fps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             l, r, _ = frame(1)
             cr = conv_roofline(runner, (l, r), device)
@@ -783,13 +824,17 @@ def main():
                        "launch_configuration_sync": tune_note or "single rank",
                        "ranks_seen": ranks_seen, "frames_timed_all_ranks": sum(r[2] for r in ranks_seen)},
             "epe_vs_synthetic_gt": red["epe"][0],
-            # every convolution on the exact-fp32 kernels (--precision fp32), same frame, shorter run
-            "fp32_exact_fps": fp32_fps,
-            "fps_two_videos_per_gpu": two_fps,
-            # two videos as ONE batch through the same launches (B = 2 lock-step), frames/s of both videos together
-            "fps_two_videos_batched": batched_fps,
-            "roofline": roof, "cpu_baseline": cpu,
         }
+        out["config"]["full"] = args.full
+        if args.full:
+            out.update({
+                # every convolution on the exact-fp32 kernels (--precision fp32), same frame, shorter run
+                "fp32_exact_fps": fp32_fps,
+                "fps_two_videos_per_gpu": two_fps,
+                # two videos as ONE batch through the same launches (B = 2 lock-step), frames/s of both videos together
+                "fps_two_videos_batched": batched_fps,
+                "roofline": roof, "cpu_baseline": cpu,
+            })
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()

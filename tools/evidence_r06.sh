@@ -10,10 +10,10 @@ python -m pytest tests/test_gpu_headline_parity.py -m gpu -q -s > $O/headline_pa
 grep -v "^$" $O/headline_parity_full.log | grep "frame\|worst\|per-frame\|passed\|failed\|golden\|held\|meet\|oracle-vs-oracle" | cut -c1-400 > $O/headline_parity.log
 { tail -3 $O/headline_parity_full.log; python -m pytest tests -m gpu -q --ignore tests/test_gpu_headline_parity.py 2>&1 | tail -8; } > $O/gpu_tests.log
 rm -f $O/headline_parity_full.log
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python -m torch.distributed.run --standalone --local-addr 127.0.0.1 --nnodes=1 --nproc-per-node 1 bench.py --gpus 1 --steps 200 --warmup 5 --no-cpu-baseline 2>/dev/null | grep "^{" > $O/bench_torchrun_n1.json
-python bench.py --stereo-only --no-cpu-baseline --steps 100 2>/dev/null > $O/bench_stereo_only.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null > $O/bench_steps20.json   # the driver's K
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python -m torch.distributed.run --standalone --local-addr 127.0.0.1 --nnodes=1 --nproc-per-node 1 bench.py --gpus 1 --steps 200 --warmup 5 --full --no-cpu-baseline 2>/dev/null | grep "^{" > $O/bench_torchrun_n1.json
+python bench.py --stereo-only --full --no-cpu-baseline --steps 100 2>/dev/null > $O/bench_stereo_only.json
+python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null > $O/bench_steps20.json   # the driver's K
 { for P in "--precision split --iters 1" "--precision fp16mix" "--precision split"; do echo "== bench.py --height 512 --width 640 $P"; python bench.py --height 512 --width 640 --no-cpu-baseline --no-pmc-traffic --two-video-steps 0 --fp32-steps 0 --steps 100 $P 2>/dev/null | cut -c1-260; done; echo "== bench.py --height 384 --width 1280"; python bench.py --height 384 --width 1280 --no-cpu-baseline --no-pmc-traffic --two-video-steps 0 --fp32-steps 0 --steps 100 2>/dev/null | cut -c1-260; } > $O/cfg_variants.log
 ROUND=r06 bash tools/profile_round.sh > $O/profile_round.log 2>&1
 S=$R/gpurun_out/prof_r06/serial_kernel_stats.csv

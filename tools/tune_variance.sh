@@ -1,7 +1,7 @@
 #!/bin/bash
 # dev aid: run bench.py several times with autotune and list, per run, fps + the tuned configuration of the big layers
 for i in 1 2 3 4 5; do
-  CODD_BENCH_VERBOSE=1 python bench.py --no-cpu-baseline > /tmp/tv_out.txt 2> /tmp/tv_err.txt
+  CODD_BENCH_VERBOSE=1 python bench.py --full --no-cpu-baseline > /tmp/tv_out.txt 2> /tmp/tv_err.txt
   python3 - <<'PY'
 import json, re
 d = json.loads(open('/tmp/tv_out.txt').read().strip().splitlines()[-1])
