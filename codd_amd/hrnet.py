@@ -103,7 +103,7 @@ class HRModule(nn.Module):
         nb = len(xs)
         xs = list(xs)
         nblk = len(self.branches[0])
-        if nb > 1 and ops.MULTI_CONV and ops.CONV_PRECISION == "fp32":
+        if nb > 1 and ops.CONV_PRECISION == "fp32":
             # step s of every branch (conv1 / conv2 of block s // 2) is independent of the other branches: one
             # multi-job launch per step (ops.conv2d_multi) instead of one ~10 us launch per branch and step
             ys, blockin = list(xs), list(xs)

@@ -3,6 +3,7 @@
 PyTorch is used for device memory and streams only; every computation below is a call into
 libcodd_hip.so.  There is no CPU / eager fallback: tensors must live on a ROCm device.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -85,48 +86,86 @@ class PackedConv:
         # 16-channel blocks per workgroup: 64-channel groups only for wide layers that fill them
         # exactly (measured: 96->96 3x3 87 us at mb=2 vs 116 us at mb=4)
         self.mb = 1 if self.cout_eff <= 16 else (4 if (self.cout_eff >= 256 and self.cout_eff % 64 == 0) else 2)
-        if _FORCE_MB and self.cout_eff > 32:
-            self.mb = _FORCE_MB
         self._w = w
         self._packs = {}
-        self.tuned = {}  # launch shape -> (npb, nw, ck)
+        self.tuned = {}  # launch shape -> stored launch configuration (decode_cfg)
 
     def packed(self, ck, mb=None, layout=0):
         """layout 0 / 1: fp32 kernels; 20 + terms (21 | 23): split-bf16 kernel with 1 | 3 product terms."""
         mb = self.mb if mb is None else mb
-        if layout >= 20 and (mb, ck, layout) not in self._packs:
-            lib = _abi.load()
-            terms = layout - 20
-            n = lib.codd_conv2d_packed_bytes_bf16(self.cout_eff, self.cin, self.kh, self.kw, mb, ck, terms)
-            if n <= 0:
-                raise _abi.CoddHipError("no split-bf16 packed layout for ck=%d mb=%d terms=%d" % (ck, mb, terms))
-            wp = torch.empty(n, device=self._w.device, dtype=torch.uint8)
-            _abi.check(lib.codd_conv2d_pack_weights_bf16(self._w.data_ptr(), wp.data_ptr(), self.cout_eff, self.cin,
-                                                         self.kh, self.kw, mb, ck, terms, self.cin * self.kh * self.kw,
-                                                         self.kh * self.kw, 1.0, _stream()), "pack_weights_bf16")
-            self._packs[(mb, ck, layout)] = wp
         if (mb, ck, layout) not in self._packs:
-            lib = _abi.load()
-            size, pack = ((lib.codd_conv2d_packed_size_quad, lib.codd_conv2d_pack_weights_quad) if layout == 1 else
-                          (lib.codd_conv2d_packed_size, lib.codd_conv2d_pack_weights))
-            n = size(self.cout_eff, self.cin, self.kh, self.kw, mb, ck)
-            if n <= 0:
-                raise _abi.CoddHipError("no packed layout %d for ck=%d mb=%d" % (layout, ck, mb))
-            wp = torch.empty(n, device=self._w.device, dtype=torch.float32)
-            _abi.check(pack(self._w.data_ptr(), wp.data_ptr(), self.cout_eff, self.cin, self.kh, self.kw, mb, ck,
-                            _stream()), "pack_weights")
+            if layout >= 20:
+                wp = _pack_bf16(self._w, self.cout_eff, self.cin, self.kh, self.kw, mb, ck, layout - 20,
+                                self.cin * self.kh * self.kw, self.kh * self.kw, 1.0)
+            else:
+                lib = _abi.load()
+                size, pack = ((lib.codd_conv2d_packed_size_quad, lib.codd_conv2d_pack_weights_quad) if layout == 1 else
+                              (lib.codd_conv2d_packed_size, lib.codd_conv2d_pack_weights))
+                n = size(self.cout_eff, self.cin, self.kh, self.kw, mb, ck)
+                if n <= 0:
+                    raise _abi.CoddHipError("no packed layout %d for ck=%d mb=%d" % (layout, ck, mb))
+                wp = torch.empty(n, device=self._w.device, dtype=torch.float32)
+                _abi.check(pack(self._w.data_ptr(), wp.data_ptr(), self.cout_eff, self.cin, self.kh, self.kw, mb, ck,
+                                _stream()), "pack_weights")
             self._packs[(mb, ck, layout)] = wp
         return self._packs[(mb, ck, layout)]
 
     def _pack_key(self, c):
-        lay = c[4] if len(c) > 4 else 0
-        return (c[3] if len(c) > 3 else self.mb, c[2], 20 + c[7] if lay == 2 else (1 if lay == 3 else lay))
+        f = decode_cfg(c, self.mb)
+        return (f.mb, f.ck, 20 + f.terms if f.layout == 2 else f.layout)
 
-    def drop_unused_packs(self):
-        """Free the packed-weight variants no tuned configuration refers to (after autotuning)."""
-        used = {self._pack_key(c) for c in self.tuned.values()}
+    def drop_unused_packs(self, keep=None):
+        """Free the packed-weight variants that neither a tuned configuration nor ``keep`` refers to (after autotuning)."""
+        used = {self._pack_key(c) for c in list(self.tuned.values()) + ([keep] if keep is not None else [])}
         for k in [k for k in self._packs if k not in used]:
             del self._packs[k]
+
+
+def _pack_bf16(w, cout, cin, kh, kw, mb, ck, terms, co_stride, ci_stride, scale):
+    """codd_conv2d_pack_weights_bf16 of the fp32 weights ``w`` ([co][ci][tap] at the given strides) -> a new byte tensor."""
+    lib = _abi.load()
+    n = lib.codd_conv2d_packed_bytes_bf16(cout, cin, kh, kw, mb, ck, terms)
+    if n <= 0:
+        raise _abi.CoddHipError("no split-bf16 packed layout for ck=%d mb=%d terms=%d" % (ck, mb, terms))
+    wp = torch.empty(n, device=w.device, dtype=torch.uint8)
+    _abi.check(lib.codd_conv2d_pack_weights_bf16(w.data_ptr(), wp.data_ptr(), cout, cin, kh, kw, mb, ck, terms, co_stride,
+                                                 ci_stride, scale, _stream()), "pack_weights_bf16")
+    return wp
+
+
+# A launch configuration is stored (pc.tuned, TUNE_DB, codd_amd/tuned/mi355x.json, AUTOTUNE_LOG) as a plain tuple:
+#   exact fp32   (npb, nw, ck[, mb[, layout]])                     layout 0 | 1, mb defaults to PackedConv.mb
+#   split-bf16   (xb, th, ck, mb, 2, pgw, cgw[, terms[, ksplit]])  terms defaults to the launch's, ksplit to 1
+# decode_cfg names the fields after codd_conv_params (for layout 2 the header's npb = xb, nw = th); the stored tuples
+# themselves are never replaced by decoded ones.
+LaunchCfg = collections.namedtuple("LaunchCfg", "npb nw ck mb layout pgw cgw terms ksplit")
+
+
+def decode_cfg(c, mb=None, terms=None):
+    """Named fields of a stored launch configuration ``c``; ``mb`` / ``terms``: the defaults of the short forms
+    (PackedConv.mb, the launch's terms).  fp32 configurations have pgw = cgw = terms = ksplit = None."""
+    if len(c) > 4 and c[4] == 2:
+        if not 7 <= len(c) <= 9:
+            raise ValueError("split-bf16 launch configuration of %d fields: %r" % (len(c), tuple(c)))
+        return LaunchCfg(c[0], c[1], c[2], c[3], 2, c[5], c[6], c[7] if len(c) > 7 else terms, c[8] if len(c) > 8 else 1)
+    if not 3 <= len(c) <= 5 or (len(c) > 4 and c[4] not in (0, 1)):
+        raise ValueError("not an exact-fp32 launch configuration: %r" % (tuple(c),))
+    return LaunchCfg(c[0], c[1], c[2], c[3] if len(c) > 3 else mb, c[4] if len(c) > 4 else 0, None, None, None, None)
+
+
+def _set_cfg(p, c, pc=None):
+    """Write launch configuration ``c`` into ``p``; with ``pc`` also its packed weights (split-bf16: packed for p.terms;
+    exact fp32: p.terms = 0).  Fields of the other family are left as they are."""
+    f = decode_cfg(c, None if pc is None else pc.mb, p.terms)
+    if f.layout == 2:
+        if pc is not None:
+            p.wpacked = pc.packed(f.ck, f.mb, 20 + p.terms).data_ptr()
+        p.pgw, p.cgw, p.ksplit = f.pgw, f.cgw, f.ksplit
+    else:
+        if pc is not None:
+            p.wpacked = pc.packed(f.ck, f.mb, f.layout).data_ptr()
+        p.terms = 0
+    p.mb, p.npb, p.nw, p.ck, p.layout = f.mb, f.npb, f.nw, f.ck, f.layout
 
 
 def _launch_conv(lib, p, stream):
@@ -135,10 +174,7 @@ def _launch_conv(lib, p, stream):
 
 
 import os as _os
-_FORCE_NPB = 0
-_FORCE_MB = 0
-_FORCE_CK = 0
-_FORCE_NW = 0
+_FORCE_NW = 0  # (tests: a workgroup height the heuristic may not pick)
 
 
 def _wrow(mb):
@@ -171,8 +207,6 @@ def _conv_cfg(pc, Hout, Wout, B, sy, sx, dy, dx, pl):
     staging: <= 16 float4 of weights and <= 8 float4 of input per thread and chunk."""
     ncog = -(-pc.cout_eff // (16 * pc.mb))
     npb = 2 if pc.cout_eff <= 16 else 1
-    if _FORCE_NPB:
-        npb = _FORCE_NPB
     nw = _pick_nw(pc, npb, Hout, Wout, B, ncog)
     nt = 64 * nw
     xb = 2 if npb >= 2 else 1
@@ -192,8 +226,6 @@ def _conv_cfg(pc, Hout, Wout, B, sy, sx, dy, dx, pl):
     while ck > 4 and ((taps * ck * _wrow(pc.mb) + ck * chs) * 4 > budget or taps * ck * _wrow(pc.mb) > 64 * nt
                       or ck * thi * (twp // 4) > (8 if nw == 4 else 4) * nt):
         ck -= 4
-    if _FORCE_CK:
-        ck = min(ck, _FORCE_CK)
     return npb, nw, ck
 
 
@@ -208,7 +240,6 @@ def _conv_cfg(pc, Hout, Wout, B, sy, sx, dy, dx, pl):
 #   "fp16"             IEEE fp16 operands (v_mfma_f32_16x16x32_f16), fp32 accumulate: the reference's own reduced
 #                      precision (auto_fp16 IS .half(), model/codd.py:37,128): 11 mantissa bits at bf16's MFMA rate
 CONV_PRECISION = "split"  # set through set_conv_precision() / bench.py --precision, never through the environment
-ALLPAIRS_SPLIT = True  # (A/B switch of allpairs_corr)
 _TERMS = dict(split=3, bf16=1, fp16=16, split16=48)  # codd_conv_params.terms (CODD_TERMS_*)
 
 
@@ -298,7 +329,8 @@ class coresident:
 
 
 def _small_footprint(cands):
-    small = [c for c in cands if c[5] * c[6] * (c[8] if len(c) > 8 else 1) == 4 and c[3] // c[6] <= 2]
+    fs = [decode_cfg(c) for c in cands]
+    small = [c for c, f in zip(cands, fs) if f.pgw * f.cgw * f.ksplit == 4 and f.mb // f.cgw <= 2]
     return small or cands
 
 
@@ -409,6 +441,31 @@ def split_buffer(key, B, C, H, W, border=0, device=None):
     return st
 
 
+def _conv_params(pc, B, C0, C1, Hin, Win, Hout, Wout, stride, pad, dil, act="none"):
+    """ConvParams of a convolution by ``pc``: geometry, bias, activation; stride / pad (top, left) / dil as (y, x)."""
+    p = ConvParams()
+    p.C0, p.C1, p.B, p.Hin, p.Win = C0, C1, B, Hin, Win
+    p.bias = None if pc.bias is None else pc.bias.data_ptr()
+    p.Cout, p.Hout, p.Wout = pc.cout, Hout, Wout
+    p.kh, p.kw, p.sy, p.sx = pc.kh, pc.kw, stride[0], stride[1]
+    p.pad_t, p.pad_l, p.dil_y, p.dil_x = pad[0], pad[1], dil[0], dil[1]
+    p.act = ACT[act]
+    p.store_mode = int(pc.deconv)
+    return p
+
+
+def _attach_xs(p, st, coff):
+    """Read the conv input from channels [coff, ...) of the SplitTensor ``st``."""
+    p.xs, p.xs_c8, p.xs_hp, p.xs_wp = st.buf.data_ptr(), st.c8, st.hp, st.wp
+    p.xs_bt, p.xs_bl, p.xs_o8 = st.bt, st.bl, coff // 8
+
+
+def _attach_xso(p, st, coff):
+    """Write the conv output as split records into channels [coff, ...) of the SplitTensor ``st``."""
+    p.xso, p.xso_c8, p.xso_hp, p.xso_wp = st.buf.data_ptr(), st.c8, st.hp, st.wp
+    p.xso_bt, p.xso_bl, p.xso_o8, p.xso_terms = st.bt, st.bl, coff // 8, st.terms
+
+
 def conv2d(x, pc, x2=None, stride=1, pad=0, dil=1, act="none", res1=None, res2=None, post=None,
            out=None, pad_tl=None, out_hw=None, xs=None, xs_coff=0, xs_out=None, xs_out_coff=0):
     """act(conv(cat[x, x2]) + bias + res1 + res2) + post  ->  out (tensor or Slice).
@@ -466,18 +523,12 @@ def conv2d(x, pc, x2=None, stride=1, pad=0, dil=1, act="none", res1=None, res2=N
         os_ = None
     key = (Hout, Wout, B, sy, sx, dy, dx, pl, C1 > 0, terms) + (("split",) if force_split else ()) + (
         ("co",) if _CORESIDENT and terms else ())
-    p = ConvParams()
+    p = _conv_params(pc, B, C0, C1, Hin, Win, Hout, Wout, (sy, sx), (pt, pl), (dy, dx), act)
     p.in0 = _view(xsl)
     p.in1 = _view(x2)
-    p.C0, p.C1, p.B, p.Hin, p.Win = C0, C1, B, Hin, Win
-    p.bias = None if pc.bias is None else pc.bias.data_ptr()
     p.res1, p.res2, p.post = _view(res1), _view(res2), _view(post)
     if os_ is not None:
         p.out, p.out_ctot, p.out_coff = os_.buf.data_ptr(), os_.buf.shape[1], os_.coff
-    p.Cout, p.Hout, p.Wout = pc.cout, Hout, Wout
-    p.kh, p.kw, p.sy, p.sx, p.pad_t, p.pad_l, p.dil_y, p.dil_x = pc.kh, pc.kw, sy, sx, pt, pl, dy, dx
-    p.act = ACT[act]
-    p.store_mode = 1 if pc.deconv else 0
     p.terms = terms
 
     cfg = pc.tuned.get(key)
@@ -486,38 +537,42 @@ def conv2d(x, pc, x2=None, stride=1, pad=0, dil=1, act="none", res1=None, res2=N
             pc.cout_eff, pc.cin, pc.kh, pc.kw, pc.mb, int(pc.deconv)) + ",".join(str(int(v)) for v in key[:9]) + (
                 "|split" if force_split else "") + ("|co" if _CORESIDENT and terms else "")
         co = _small_footprint if _CORESIDENT else (lambda c: c)
-        capturing = torch.cuda.is_current_stream_capturing()
-        if _AUTOTUNE and sig in TUNE_DB and _db_cfg_ok(lib, p, TUNE_DB[sig], sig):
-            cfg = pc.tuned[key] = tuple(TUNE_DB[sig])  # same layer signature already timed (this process or a loaded file)
-        elif force_split:
+
+        def split_cands():
+            return co([c for c in _bf16_candidates(pc, Hout, Wout, B, pc.kh * pc.kw, terms) if _cfg_ok(lib, p, c)])
+
+        def heuristic():
+            return _conv_cfg(pc, Hout, Wout, B, sy, sx, dy, dx, pl)
+
+        if force_split:
             # pinned to the split-bf16 kernel: the configuration this layer was tuned to in its plain form if that is
             # a split one, else the first candidate the library accepts
-            cands = co([c for c in _bf16_candidates(pc, Hout, Wout, B, pc.kh * pc.kw, terms) if _cfg_ok(lib, p, c)])
-            if not cands:
-                raise _abi.CoddHipError("no split-bf16 launch configuration for conv %dx%d %d->%d" % (
-                    pc.kh, pc.kw, pc.cin, pc.cout))
-            if _AUTOTUNE and not capturing:  # time the candidates on the real split input / output tensors
+            def pinned_cands():
+                cands = split_cands()
+                if not cands:
+                    raise _abi.CoddHipError("no split-bf16 launch configuration for conv %dx%d %d->%d" % (
+                        pc.kh, pc.kw, pc.cin, pc.cout))
+                return cands
+
+            def tune_pinned(cands):  # time the candidates on the real split input / output tensors
+                keep = None if x is None else _make_split(lib, p, xsl, x2, cands)  # noqa: F841
                 if x is None:
-                    p.xs, p.xs_c8, p.xs_hp, p.xs_wp = xs.buf.data_ptr(), xs.c8, xs.hp, xs.wp
-                    p.xs_bt, p.xs_bl, p.xs_o8 = xs.bt, xs.bl, xs_coff // 8
-                else:
-                    keep = _make_split(lib, p, xsl, x2, cands)  # noqa: F841
+                    _attach_xs(p, xs, xs_coff)
                 if xs_out is not None:
-                    p.xso, p.xso_c8, p.xso_hp, p.xso_wp = xs_out.buf.data_ptr(), xs_out.c8, xs_out.hp, xs_out.wp
-                    p.xso_bt, p.xso_bl, p.xso_o8, p.xso_terms = xs_out.bt, xs_out.bl, xs_out_coff // 8, xs_out.terms
-                cfg, _ = _autotune_b(lib, p, pc, cands, None, None)
-                TUNE_DB[sig] = cfg
-            else:
+                    _attach_xso(p, xs_out, xs_out_coff)
+                return _autotune_b(lib, p, pc, cands, None, None)[0]
+
+            def untimed(cands):
                 plain = TUNE_DB.get(sig[:-6]) if _AUTOTUNE and not _CORESIDENT else None
-                cfg = tuple(plain) if plain is not None and len(plain) > 4 and plain[4] == 2 else cands[0]
-            pc.tuned[key] = cfg
+                return tuple(plain) if plain is not None and decode_cfg(plain).layout == 2 else cands[0]
+
+            # (kept in pc.tuned even when picked while capturing with autotune on)
+            cfg = pc.tuned[key] = _pick_cfg(lib, p, pc, key, sig, pinned_cands, tune_pinned, untimed)
         elif terms:
-            cands = co([c for c in _bf16_candidates(pc, Hout, Wout, B, pc.kh * pc.kw, terms) if _cfg_ok(lib, p, c)])
-            if _AUTOTUNE and not capturing:
+            def tune_choice(cands):
                 # measure: best split-bf16 configuration (incl. its re-layout pass) against the best exact-fp32 one --
                 # small or large-map layers can be faster (and are more exact) on the fp32 kernels
-                h32 = _conv_cfg(pc, Hout, Wout, B, sy, sx, dy, dx, pl)
-                f32cfg, t32 = _autotune(lib, p, pc, h32 + (pc.mb, 0), with_time=True)
+                f32cfg, t32 = _autotune(lib, p, pc, heuristic() + (pc.mb, 0))
                 p.terms = terms
                 bcfg, tb = (None, float("inf"))
                 if cands:
@@ -526,51 +581,58 @@ def conv2d(x, pc, x2=None, stride=1, pad=0, dil=1, act="none", res1=None, res2=N
                 cfg = bcfg if tb < t32 else f32cfg
                 AUTOTUNE_LOG.append(("choice %dx%d %d->%d out %dx%d" % (pc.kh, pc.kw, pc.cin, pc.cout, Hout, Wout),
                                      f32cfg, t32 * 1e3, cfg, min(tb, t32) * 1e3))
-                pc.tuned[key] = TUNE_DB[sig] = cfg
-            else:
-                cfg = cands[0] if cands else _conv_cfg(pc, Hout, Wout, B, sy, sx, dy, dx, pl) + (pc.mb, 0)
-                if not _AUTOTUNE:
-                    pc.tuned[key] = cfg  # (capturing with autotune on: heuristic for this launch, tune later)
-        else:
-            cfg = _conv_cfg(pc, Hout, Wout, B, sy, sx, dy, dx, pl)
-            if _AUTOTUNE and not capturing:
-                cfg = TUNE_DB[sig] = _autotune(lib, p, pc, cfg + (pc.mb, 0))
-            if not _AUTOTUNE or not capturing:
-                pc.tuned[key] = cfg
+                return cfg
 
-    if len(cfg) > 4 and cfg[4] == 2:  # split-bf16 / bf16 kernel
+            cfg = _pick_cfg(lib, p, pc, key, sig, split_cands, tune_choice,
+                            lambda cands: cands[0] if cands else heuristic() + (pc.mb, 0))
+        else:
+            cfg = _pick_cfg(lib, p, pc, key, sig, lambda: [heuristic()],
+                            lambda cands: _autotune(lib, p, pc, cands[0] + (pc.mb, 0))[0])
+
+    if decode_cfg(cfg).layout == 2:  # split-bf16 / bf16 kernel
         keep = None
         if xs_out is not None:
-            p.xso, p.xso_c8, p.xso_hp, p.xso_wp = xs_out.buf.data_ptr(), xs_out.c8, xs_out.hp, xs_out.wp
-            p.xso_bt, p.xso_bl, p.xso_o8, p.xso_terms = xs_out.bt, xs_out.bl, xs_out_coff // 8, xs_out.terms
+            _attach_xso(p, xs_out, xs_out_coff)
             out = xs_out
         if (xs is not None and xs.terms == terms and (xs.B, xs.H, xs.W) == (B, Hin, Win) and xs_coff % 8 == 0 and
                 xs_coff + pc.cin <= max(xs.C, 8 * xs.c8 if x is None else 0)):
-            p.xs, p.xs_c8, p.xs_hp, p.xs_wp = xs.buf.data_ptr(), xs.c8, xs.hp, xs.wp
-            p.xs_bt, p.xs_bl, p.xs_o8 = xs.bt, xs.bl, xs_coff // 8
-            _set_cfg(p, pc, cfg)
+            _attach_xs(p, xs, xs_coff)
+            _set_cfg(p, cfg, pc)
             rc = _launch_conv(lib, p, _stream())
             if rc == 0:
                 return out
             if rc != -1 or x is None:  # -1: the shared tensor does not fit this configuration's tiles -> private re-layout below
                 _abi.check(rc, "codd_conv2d")
         keep = _make_split(lib, p, xsl, x2, [cfg])  # noqa: F841 (alive until the launch below is enqueued)
-        _set_cfg(p, pc, cfg)
+        _set_cfg(p, cfg, pc)
         _abi.check(_launch_conv(lib, p, _stream()), "codd_conv2d")
         return out
-    npb, nw, ck = cfg[:3]
-    mb = cfg[3] if len(cfg) > 3 else pc.mb
-    layout = cfg[4] if len(cfg) > 4 else 0
-    p.terms = 0
-    p.wpacked = pc.packed(ck, mb, layout).data_ptr()
-    p.mb, p.npb, p.nw, p.ck, p.layout = mb, npb, nw, ck, layout
+    _set_cfg(p, cfg, pc)
     heur = (key, (Hout, Wout, B, sy, sx, dy, dx, pl))
-    if _DEFERRED is not None and layout == 1 and npb == 1 and nw == 4 and mb == 1:
+    if _DEFERRED is not None and p.layout == 1 and p.npb == 1 and p.nw == 4 and p.mb == 1:
         # inside ``with deferred_convs():`` -- recorded, launched on exit together with its independent neighbours
         _DEFERRED.append((ConvParams.from_buffer_copy(p), (x, x2, res1, res2, post, out), pc, heur))
         return out
     _launch_fp32(lib, p, pc, heur)
     return out
+
+
+def _pick_cfg(lib, p, pc, key, sig, candidates, tune, untimed=None):
+    """Launch configuration of a conv2d / conv_gate launch shape met for the first time (``key`` in pc.tuned, layer
+    signature ``sig`` in TUNE_DB): the tune-db entry when this build accepts it; else, autotuning and not capturing,
+    tune(candidates()), recorded in TUNE_DB; else untimed(candidates()), by default the first candidate.  The pick is
+    kept in pc.tuned, except an untimed one while capturing with autotune on (this launch only, timed later)."""
+    if _AUTOTUNE and sig in TUNE_DB and _db_cfg_ok(lib, p, TUNE_DB[sig], sig):
+        cfg = pc.tuned[key] = tuple(TUNE_DB[sig])  # same layer signature already timed (this process or a loaded file)
+        return cfg
+    cands = candidates()
+    if _AUTOTUNE and not torch.cuda.is_current_stream_capturing():
+        cfg = pc.tuned[key] = TUNE_DB[sig] = tune(cands)
+        return cfg
+    cfg = cands[0] if untimed is None else untimed(cands)
+    if not _AUTOTUNE:
+        pc.tuned[key] = cfg
+    return cfg
 
 
 def _launch_fp32(lib, p, pc, heur):
@@ -583,9 +645,8 @@ def _launch_fp32(lib, p, pc, heur):
         key, geom = heur
         warnings.warn("codd_amd: launch configuration %s rejected for conv %dx%d %d->%d, using the heuristic" % (
             (p.npb, p.nw, p.ck, p.mb, p.layout), pc.kh, pc.kw, pc.cin, pc.cout))
-        npb, nw, ck = pc.tuned[key] = _conv_cfg(pc, *geom)
-        p.wpacked = pc.packed(ck, pc.mb, 0).data_ptr()
-        p.mb, p.npb, p.nw, p.ck, p.layout = pc.mb, npb, nw, ck, 0
+        cfg = pc.tuned[key] = _conv_cfg(pc, *geom)
+        _set_cfg(p, cfg, pc)
         rc = _launch_conv(lib, p, _stream())
     _abi.check(rc, "codd_conv2d")
 
@@ -595,19 +656,18 @@ def _db_cfg_ok(lib, p, c, sig):
     may name tiles that no longer exist): split-bf16 entries are probed with codd_conv2d_check (fp32 entries are
     validated at launch, rc -2 -> heuristic); a rejected entry is dropped with a warning and the layer is tuned /
     given the heuristic as if the db had no entry."""
-    if len(c) > 4 and c[4] == 2:
-        if not p.terms or (len(c) > 7 and c[7] != p.terms) or not _cfg_ok(lib, p, c):
-            import warnings
-            warnings.warn("codd_amd: tune-db entry %s = %s is not a valid split-bf16 configuration of this build; ignored" % (
-                sig, tuple(c)))
-            del TUNE_DB[sig]
-            return False
+    try:
+        f = decode_cfg(c, terms=p.terms)
+    except ValueError:
+        f = None
+    if f is None or (f.layout == 2 and (not p.terms or f.terms != p.terms or not _cfg_ok(lib, p, c))):
+        import warnings
+        warnings.warn("codd_amd: tune-db entry %s = %s is not a valid %s configuration of this build; ignored" % (
+            sig, tuple(c), "launch" if f is None else "split-bf16"))
+        del TUNE_DB[sig]
+        return False
     return True
 
-
-MULTI_CONV = True  # (A/B switch of conv2d_multi)
-MULTI_DEEP_FIRST = True  # (A/B: job order inside a multi-job launch)
-MULTI_MB = 1  # 16-channel blocks per workgroup of a multi-job launch (1 | 2)
 
 _DEFERRED = None
 
@@ -631,25 +691,33 @@ class deferred_convs:
         if exc[0] is not None or not items:
             return False
         lib = _abi.load()
-        for k0 in range(0, len(items), 4):
-            chunk = items[k0:k0 + 4]
-            if MULTI_DEEP_FIRST:
-                chunk = sorted(chunk, key=lambda c: -((c[0].C0 + c[0].C1) * c[0].kh * c[0].kw))
-            rc = -2
-            if len(chunk) > 1 and MULTI_CONV:
-                arr = (ConvParams * len(chunk))(*[c[0] for c in chunk])
-                rc = _launch_conv_multi(lib, arr, len(chunk), _stream())
-                if rc not in (0, -2):
-                    _abi.check(rc, "codd_conv2d_multi (deferred)")
-            if rc != 0:  # one job, or a multi-job launch this build rejects: single launches with conv2d's own fallback
-                for pp, _, pc, heur in chunk:
-                    _launch_fp32(lib, pp, pc, heur)
+        # one job, or a multi-job launch this build rejects: single launches with conv2d's own fallback
+        _launch_multi(lib, items, lambda it: _launch_fp32(lib, it[0], it[2], it[3]), "codd_conv2d_multi (deferred)")
         return False
 
 
 def _launch_conv_multi(lib, params, n, stream):
     """Single choke point of the multi-job conv launches (bench.py wraps it with HIP events)."""
     return lib.codd_conv2d_multi(params, n, stream)
+
+
+def _launch_multi(lib, jobs, fallback, what):
+    """Launch ``jobs`` -- tuples whose first item is the ConvParams of a convolution of the multi-job class -- up to four
+    at a time, in the order given, each group as ONE codd_conv2d_multi; a lone job and every job of a group this build
+    rejects (rc -2) go to ``fallback(job)`` instead.  Workgroups are dispatched in job order: inside a group the job with
+    the longest per-workgroup chain (most input channels x taps) goes first, so that its chain runs beside the wide,
+    shallow jobs instead of after them."""
+    for k0 in range(0, len(jobs), 4):
+        group = sorted(jobs[k0:k0 + 4], key=lambda j: -((j[0].C0 + j[0].C1) * j[0].kh * j[0].kw))
+        rc = -2
+        if len(group) > 1:
+            arr = (ConvParams * len(group))(*[j[0] for j in group])
+            rc = _launch_conv_multi(lib, arr, len(group), _stream())
+            if rc not in (0, -2):
+                _abi.check(rc, what)
+        if rc != 0:
+            for j in group:
+                fallback(j)
 
 
 def conv2d_multi(jobs):
@@ -660,48 +728,31 @@ def conv2d_multi(jobs):
     lib = _abi.load()
     outs = [None] * len(jobs)
     group = []
-    if MULTI_CONV and CONV_PRECISION == "fp32" and len(jobs) > 1:
-        for idx, j in enumerate(jobs):
-            x, pc = j["x"], j["pc"]
-            if (isinstance(x, torch.Tensor) and x.shape[3] % 4 == 0 and x.data_ptr() % 16 == 0 and not pc.deconv
-                    and pc.cin >= 16 and j.get("stride", 1) in (1, 2)):
-                group.append(idx)
-    for k0 in range(0, len(group), 4):
-        ids = group[k0:k0 + 4]
-        if len(ids) < 2:
-            break
-        if MULTI_DEEP_FIRST:
-            # workgroups are dispatched in job order: the job with the longest per-workgroup chain (most chunks x taps)
-            # goes first, so that its chain runs beside the wide, shallow jobs instead of after them
-            ids = sorted(ids, key=lambda i_: -(jobs[i_]["pc"].cin * jobs[i_]["pc"].kh * jobs[i_]["pc"].kw))
-        arr = (ConvParams * len(ids))()
-        keep = []
-        for slot, idx in enumerate(ids):
-            j = jobs[idx]
-            x, pc = j["x"], j["pc"]
-            B, C0, Hin, Win = x.shape
-            st, pad = j.get("stride", 1), j.get("pad", 0)
-            Hout = (Hin + 2 * pad - (pc.kh - 1) - 1) // st + 1
-            Wout = (Win + 2 * pad - (pc.kw - 1) - 1) // st + 1
-            out = torch.empty(B, pc.cout, Hout, Wout, device=x.device, dtype=torch.float32)
-            ck = 32 if pc.cin > 16 else 16
-            p = arr[slot]
-            p.in0, p.C0, p.C1, p.B, p.Hin, p.Win = _view(x), C0, 0, B, Hin, Win
-            p.bias = None if pc.bias is None else pc.bias.data_ptr()
-            p.res1 = _view(j.get("res1"))
-            p.out, p.out_ctot, p.out_coff = out.data_ptr(), pc.cout, 0
-            p.Cout, p.Hout, p.Wout = pc.cout, Hout, Wout
-            p.kh, p.kw, p.sy, p.sx, p.pad_t, p.pad_l, p.dil_y, p.dil_x = pc.kh, pc.kw, st, st, pad, pad, 1, 1
-            p.act = ACT[j.get("act", "none")]
-            p.mb, p.npb, p.nw, p.ck, p.layout = MULTI_MB, 1, 4, ck, 1
-            p.wpacked = pc.packed(ck, MULTI_MB, 1).data_ptr()
-            keep.append(out)
-        rc = _launch_conv_multi(lib, arr, len(ids), _stream())
-        if rc == 0:
-            for idx, out in zip(ids, keep):
-                outs[idx] = out
-        elif rc != -2:
-            _abi.check(rc, "codd_conv2d_multi")
+    if CONV_PRECISION == "fp32" and len(jobs) > 1:
+        group = [idx for idx, j in enumerate(jobs)
+                 if (isinstance(j["x"], torch.Tensor) and j["x"].shape[3] % 4 == 0 and j["x"].data_ptr() % 16 == 0
+                     and not j["pc"].deconv and j["pc"].cin >= 16 and j.get("stride", 1) in (1, 2))]
+        if len(group) % 4 == 1:
+            group.pop()  # a lone last job goes through conv2d
+    multi = []
+    for idx in group:
+        j = jobs[idx]
+        x, pc = j["x"], j["pc"]
+        B, C0, Hin, Win = x.shape
+        st, pad = j.get("stride", 1), j.get("pad", 0)
+        Hout = (Hin + 2 * pad - (pc.kh - 1) - 1) // st + 1
+        Wout = (Win + 2 * pad - (pc.kw - 1) - 1) // st + 1
+        out = outs[idx] = torch.empty(B, pc.cout, Hout, Wout, device=x.device, dtype=torch.float32)
+        p = _conv_params(pc, B, C0, 0, Hin, Win, Hout, Wout, (st, st), (pad, pad), (1, 1), j.get("act", "none"))
+        p.in0, p.res1 = _view(x), _view(j.get("res1"))
+        p.out, p.out_ctot, p.out_coff = out.data_ptr(), pc.cout, 0
+        _set_cfg(p, (1, 4, 32 if pc.cin > 16 else 16, 1, 1), pc)
+        multi.append((p, idx))
+
+    def later(job):  # rejected group: through conv2d below
+        outs[job[1]] = None
+
+    _launch_multi(lib, multi, later, "codd_conv2d_multi")
     for idx, j in enumerate(jobs):
         if outs[idx] is None:
             outs[idx] = conv2d(j["x"], j["pc"], stride=j.get("stride", 1), pad=j.get("pad", 0), act=j.get("act", "none"),
@@ -761,29 +812,21 @@ def conv_gate(pc, xs, gate, pad=0, dil=1, dil2=0, out=None, out_coff=0, res1=Non
         raise _abi.CoddHipError("gate-epilogue convolutions need the 'split' or 'bf16' conv precision")
     _require_gpu(xs.buf)
     B, H, W = xs.B, xs.H, xs.W
-    p = ConvParams()
-    p.C0, p.C1, p.B, p.Hin, p.Win = pc.cin, 0, B, H, W
-    p.bias = None if pc.bias is None else pc.bias.data_ptr()
-    p.Cout, p.Hout, p.Wout = pc.cout, H, W
-    p.kh, p.kw, p.sy, p.sx, p.pad_t, p.pad_l, p.dil_y, p.dil_x = pc.kh, pc.kw, 1, 1, pad, pad, dil, dil
+    p = _conv_params(pc, B, pc.cin, 0, H, W, H, W, (1, 1), (pad, pad), (dil, dil))
     p.dil2, p.gate, p.terms, p.layout = dil2, gate, terms, 2
     p.out, p.out_ctot, p.out_coff = out.buf.data_ptr(), out.C, out_coff
     for name, t in (("res1", res1), ("res2", res2), ("post", post)):
         if t is not None:
             setattr(p, name, t.view())
-    p.xs, p.xs_c8, p.xs_hp, p.xs_wp = xs.buf.data_ptr(), xs.c8, xs.hp, xs.wp
-    p.xs_bt, p.xs_bl, p.xs_o8 = xs.bt, xs.bl, xs_coff // 8
+    _attach_xs(p, xs, xs_coff)
     if xs_out is not None:
-        p.xso, p.xso_c8, p.xso_hp, p.xso_wp = xs_out.buf.data_ptr(), xs_out.c8, xs_out.hp, xs_out.wp
-        p.xso_bt, p.xso_bl, p.xso_o8, p.xso_terms = xs_out.bt, xs_out.bl, 0, xs_out.terms
+        _attach_xso(p, xs_out, 0)
     key = ("gate", gate, H, W, B, pad, dil, dil2, terms)
     cfg = pc.tuned.get(key)
     if cfg is None:
         sig = "g%d,b%d|%d,%d,%d,%d|%d,%d,%d,%d,%d,%d" % (gate, terms, pc.cout, pc.cin, pc.kh, pc.kw, H, W, B, pad, dil, dil2)
-        capturing = torch.cuda.is_current_stream_capturing()
-        if _AUTOTUNE and sig in TUNE_DB and _db_cfg_ok(lib, p, TUNE_DB[sig], sig):
-            cfg = tuple(TUNE_DB[sig])
-        else:
+
+        def candidates():
             cands = [c for c in _bf16_candidates(pc, H, W, B, pc.kh * pc.kw, terms) if _cfg_ok(lib, p, c)]
             if gate == 1:
                 # the z|r convolution runs BESIDE the VALU-only Gauss-Newton builder (BasicUpdateBlock.zr_convs): a
@@ -795,31 +838,19 @@ def conv_gate(pc, xs, gate, pad=0, dil=1, dil2=0, out=None, out_coff=0, res1=Non
             if not cands:
                 raise _abi.CoddHipError("no split-bf16 launch configuration for gate conv %dx%d %d->%d" % (
                     pc.kh, pc.kw, pc.cin, pc.cout))
-            if _AUTOTUNE and not capturing:
-                cfg, _ = _autotune_b(lib, p, pc, cands, None, None)  # (times into a scratch ``out``: in-place gates are safe)
-                TUNE_DB[sig] = cfg
-            else:
-                cfg = cands[0]
-        if not capturing or not _AUTOTUNE:
-            pc.tuned[key] = cfg
-    _set_cfg(p, pc, cfg)
+            return cands
+
+        # (times into a scratch ``out``: in-place gates are safe)
+        cfg = _pick_cfg(lib, p, pc, key, sig, candidates, lambda cands: _autotune_b(lib, p, pc, cands, None, None)[0])
+    _set_cfg(p, cfg, pc)
     _abi.check(_launch_conv(lib, p, _stream()), "codd_conv2d (gate %d)" % gate)
     return out
 
 
 def _cfg_ok(lib, p, c):
     """Does the library accept split-bf16 configuration ``c`` for the layer described by ``p``? (nothing is launched)"""
-    p.npb, p.nw, p.ck, p.mb, p.layout, p.pgw, p.cgw = c[:7]
-    p.ksplit = c[8] if len(c) > 8 else 1
+    _set_cfg(p, c)
     return lib.codd_conv2d_check(C.byref(p)) == 0
-
-
-def _set_cfg(p, pc, c):
-    """Fill the launch-configuration fields of ``p`` from a split-bf16 configuration tuple."""
-    xb, th, ck, mb, _, pgw, cgw = c[:7]
-    p.wpacked = pc.packed(ck, mb, 20 + p.terms).data_ptr()
-    p.mb, p.npb, p.nw, p.ck, p.layout, p.pgw, p.cgw = mb, xb, th, ck, 2, pgw, cgw
-    p.ksplit = c[8] if len(c) > 8 else 1
 
 
 def _split_dims(p, cands):
@@ -828,39 +859,50 @@ def _split_dims(p, cands):
     cin = p.C0 + p.C1
     c8 = hp = wp = 0
     for c in cands:
-        xb, th, ck = c[0], c[1], c[2]
-        c8 = max(c8, -(-cin // ck) * (ck // 8))
-        hp = max(hp, p.pad_t + p.Hin, (-(-p.Hout // th) * th - 1) * p.sy + (p.kh - 1) * p.dil_y + 1)
-        wp = max(wp, p.pad_l + p.Win, (-(-p.Wout // (16 * xb)) * 16 * xb - 1) * p.sx + (p.kw - 1) * p.dil_x + 1)
+        f = decode_cfg(c)
+        c8 = max(c8, -(-cin // f.ck) * (f.ck // 8))
+        hp = max(hp, p.pad_t + p.Hin, (-(-p.Hout // f.nw) * f.nw - 1) * p.sy + (p.kh - 1) * p.dil_y + 1)
+        wp = max(wp, p.pad_l + p.Win, (-(-p.Wout // (16 * f.npb)) * 16 * f.npb - 1) * p.sx + (p.kw - 1) * p.dil_x + 1)
     return c8, hp, wp
 
 
-def _make_split(lib, p, xs, x2, cands):
-    """Run codd_split_bf16 for the conv input (x | x2) and attach the result to ``p``; returns the buffer (the
-    caller keeps it alive until the conv is enqueued -- the caching allocator is stream-ordered)."""
+def _make_split(lib, p, x, x2, cands, B=None):
+    """codd_split_bf16 of the conv input (x | x2) -- B images, default p.B -- sized for every configuration in ``cands``
+    of the conv described by ``p`` (borders pad_t / pad_l), attached to ``p``.  Returns the SplitTensor: the caller
+    keeps it alive until the conv is enqueued (the caching allocator is stream-ordered)."""
+    B = p.B if B is None else B
     c8, hp, wp = _split_dims(p, cands)
-    n = lib.codd_split_bf16_bytes(p.B, c8, hp, wp, p.terms)
-    buf = torch.empty(n, device=xs.buf.device, dtype=torch.uint8)
-    _abi.check(lib.codd_split_bf16(_view(xs), p.C0, _view(x2), p.C1, p.B, p.Hin, p.Win, p.pad_t, p.pad_l, c8, hp, wp,
+    buf = torch.empty(lib.codd_split_bf16_bytes(B, c8, hp, wp, p.terms), device=_as_slice(x).buf.device,
+                      dtype=torch.uint8)
+    _abi.check(lib.codd_split_bf16(_view(x), p.C0, _view(x2), p.C1, B, p.Hin, p.Win, p.pad_t, p.pad_l, c8, hp, wp,
                                    p.terms, buf.data_ptr(), _stream()), "codd_split_bf16")
-    p.xs, p.xs_c8, p.xs_hp, p.xs_wp = buf.data_ptr(), c8, hp, wp
-    p.xs_bt, p.xs_bl, p.xs_o8 = p.pad_t, p.pad_l, 0
-    return buf
+    st = SplitTensor(buf, B, p.C0 + p.C1, p.Hin, p.Win, p.pad_t, p.pad_l, hp, wp, c8, p.terms)
+    _attach_xs(p, st, 0)
+    return st
 
 
-def _autotune_b(lib, p, pc, cands, xsl, x2):
-    """Time every split-bf16 candidate the library accepts (scratch output, see _autotune) and keep the fastest;
-    returns (configuration, ms) where the time includes the layer's own re-layout pass (codd_split_bf16)."""
+def _time_cfgs(lib, p, pc, cands, apply, desc):
+    """Time the launch configurations ``cands`` of the conv described by ``p`` and keep the fastest.  ``apply(c)`` sets
+    ``p`` up for candidate c (what it returns is kept alive while c is timed) or raises CoddHipError to skip it.  The
+    launches write into a scratch output: the real one may alias an operand (in-place accumulation "out = conv(x) +
+    out"), which repeated launches would accumulate over and over.  The first candidate runs once more first, to warm
+    clocks and caches; a candidate's time is the best of two bursts of three launches, and a later candidate must be
+    3 % faster to win (ties go to the earlier, heuristic-first candidates).  Frees pc's packed weights of the losers
+    (pc may be None) and logs (desc, first candidate, its us | None, winner, us) to AUTOTUNE_LOG.
+    -> (winner, ms); (cands[0], inf) when no candidate launches."""
     stream = _stream()
     real_out = p.out
-    scratch_out = torch.empty(p.B * p.out_ctot * (4 if p.store_mode else 1) * p.Hout * p.Wout, device=pc._w.device,
-                              dtype=torch.float32)
+    scratch_out = torch.empty(p.B * p.out_ctot * (4 if p.store_mode else 1) * p.Hout * p.Wout,
+                              device="cuda" if pc is None else pc._w.device, dtype=torch.float32)
     p.out = scratch_out.data_ptr()
-    torch.cuda.synchronize()
-    best, best_t, first = None, float("inf"), None
-    for c in cands[:1] + cands:  # first candidate twice: the first pass warms clocks / caches
-        _set_cfg(p, pc, c)
-        if _launch_conv(lib, p, stream) != 0:
+    torch.cuda.synchronize()  # nothing else on the device while the candidates are timed
+    best, best_t, t_first = cands[0], float("inf"), None
+    for i, c in enumerate(cands[:1] + cands):
+        try:
+            keep = apply(c)  # noqa: F841
+        except _abi.CoddHipError:
+            continue
+        if _launch_conv(lib, p, stream) != 0:  # not instantiated / LDS or staging limits: skip
             continue
         t = float("inf")
         for _rep in range(2):
@@ -871,21 +913,31 @@ def _autotune_b(lib, p, pc, cands, xsl, x2):
             e.record()
             e.synchronize()
             t = min(t, s.elapsed_time(e) / 3.0)
-        if first is None:
-            first = (c, t)
-            continue
-        if AUTOTUNE_TRACE is not None:
-            xb_, th_, mb_ = c[0], c[1], c[3]
-            AUTOTUNE_TRACE.append(("b%d g%d k%dx%d d%d/%d %d->%d out %dx%d" % (p.terms, p.gate, pc.kh, pc.kw, p.dil_y, p.dil2, pc.cin, pc.cout, p.Hout, p.Wout), c,
-                                   -(-p.Hout // th_) * -(-p.Wout // (16 * xb_)) * -(-pc.cout_eff // (16 * mb_)) * p.B, t * 1e3))
-        if t < best_t * 0.97 or best is None:
+        if i == 0:
+            continue  # warm-up pass
+        if i == 1:
+            t_first = t
+        if AUTOTUNE_TRACE is not None and p.layout == 2:
+            cout_eff = p.Cout * (4 if p.store_mode else 1)
+            AUTOTUNE_TRACE.append(("b%d g%d k%dx%d d%d/%d %d->%d out %dx%d" % (
+                p.terms, p.gate, p.kh, p.kw, p.dil_y, p.dil2, p.C0 + p.C1, p.Cout, p.Hout, p.Wout), c,
+                -(-p.Hout // p.nw) * -(-p.Wout // (16 * p.npb)) * -(-cout_eff // (16 * p.mb)) * p.B, t * 1e3))
+        if t < best_t * 0.97:
             best, best_t = c, t
     p.out = real_out
-    if best is None:
+    if pc is not None:
+        pc.drop_unused_packs(keep=best)
+    AUTOTUNE_LOG.append((desc, cands[0], None if t_first is None else t_first * 1e3, best, best_t * 1e3))
+    return best, best_t
+
+
+def _autotune_b(lib, p, pc, cands, xsl, x2):
+    """Time every split-bf16 candidate (_time_cfgs) and keep the fastest; returns (configuration, ms) where the time
+    includes the layer's own re-layout pass (codd_split_bf16) when ``xsl`` is given."""
+    best, best_t = _time_cfgs(lib, p, pc, cands, lambda c: _set_cfg(p, c, pc), "b%d %dx%d k%dx%d %d->%d out %dx%d" % (
+        p.terms, p.sy, p.sx, pc.kh, pc.kw, pc.cin, pc.cout, p.Hout, p.Wout))
+    if best_t == float("inf"):
         raise _abi.CoddHipError("no split-bf16 launch configuration for conv %dx%d %d->%d" % (pc.kh, pc.kw, pc.cin, pc.cout))
-    used = {pc._pack_key(c) for c in pc.tuned.values()} | {pc._pack_key(best)}
-    for k in [k for k in pc._packs if k not in used]:
-        del pc._packs[k]
     # the re-layout pass of the winner (private tensor of exactly its size); none when the input exists in split form
     t_split = 0.0
     if xsl is not None:
@@ -897,17 +949,15 @@ def _autotune_b(lib, p, pc, cands, xsl, x2):
         e.record()
         e.synchronize()
         t_split = s.elapsed_time(e) / 3.0
-    AUTOTUNE_LOG.append(("b%d %dx%d k%dx%d %d->%d out %dx%d" % (p.terms, p.sy, p.sx, pc.kh, pc.kw, pc.cin, pc.cout, p.Hout,
-                                                                p.Wout), first[0], first[1] * 1e3, best, best_t * 1e3))
     return best, best_t + t_split
 
 
 _AUTOTUNE = False  # enable_autotune()
 AUTOTUNE_LOG = []  # (layer description, heuristic cfg, us, chosen cfg, us) of every tuned launch shape
-AUTOTUNE_TRACE = None  # dev (tools/sweep_update_block.py): a list collects (layer description, cfg, grid, us) of EVERY candidate timed
+AUTOTUNE_TRACE = None  # dev (tools/sweep_update_block.py): a list collects (layer description, cfg, grid, us) of EVERY split-bf16 candidate timed
 
 
-TUNE_DB = {}  # layer signature "cout,cin,kh,kw,mb,deconv|launch shape" -> (npb, nw, ck)
+TUNE_DB = {}  # layer signature "cout,cin,kh,kw,mb,deconv|launch shape" -> stored launch configuration (decode_cfg)
 
 
 def save_tune_db(path):
@@ -940,7 +990,9 @@ def enable_autotune(flag=True, shipped=True):
             pass
 
 
-def _autotune(lib, p, pc, default, with_time=False):
+def _autotune(lib, p, pc, default):
+    """-> (configuration, ms): the heuristic exact-fp32 configuration ``default`` (npb, nw, ck, mb, layout) timed against
+    every other one the kernels are instantiated for (_time_cfgs)."""
     p.terms = 0
     cin_pad = -(-pc.cin // 4) * 4
     cks = sorted({c for c in (8, 12, 16, 24, 32) if c <= cin_pad} | {min(cin_pad, 32)})
@@ -958,46 +1010,8 @@ def _autotune(lib, p, pc, default, with_time=False):
                 for ck in (16, 32):
                     if ck <= max(16, cin_pad):
                         cands.append((npb, nw, ck, mb, 1))
-    stream = _stream()
-    # the timed launches write into a scratch copy of the output buffer: the real one may alias an operand
-    # (in-place accumulation "out = conv(x) + out"), which repeated launches would accumulate over and over
-    real_out = p.out
-    scratch_out = torch.empty(p.B * p.out_ctot * (4 if p.store_mode else 1) * p.Hout * p.Wout, device=pc._w.device,
-                              dtype=torch.float32)
-    p.out = scratch_out.data_ptr()
-    torch.cuda.synchronize()  # nothing else on the device while the candidates are timed
-    best, best_t, t_default = default, float("inf"), None
-    for (npb, nw, ck, mb, layout) in [default] + cands:  # the heuristic is timed twice (first = warm-up of clocks / caches)
-        try:
-            p.wpacked = pc.packed(ck, mb, layout).data_ptr()
-        except Exception:
-            continue
-        p.mb, p.npb, p.nw, p.ck, p.layout = mb, npb, nw, ck, layout
-        if _launch_conv(lib, p, stream) != 0:  # not instantiated / LDS or staging limits: skip
-            continue
-        t = float("inf")
-        for _rep in range(2):  # best of two bursts of three launches
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(3):
-                _launch_conv(lib, p, stream)
-            e.record()
-            e.synchronize()
-            t = min(t, s.elapsed_time(e) / 3.0)
-        if (npb, nw, ck, mb, layout) == default:
-            if t_default is None:
-                t_default = t
-                continue  # warm-up pass
-            t_default = t
-        if t < best_t * 0.97 or best_t == float("inf"):  # 3 % hysteresis: earlier (heuristic-first) candidates win ties
-            best, best_t = (npb, nw, ck, mb, layout), t
-    used = {pc._pack_key(c) for c in pc.tuned.values()} | {pc._pack_key(best)}
-    for k in [k for k in pc._packs if k not in used]:
-        del pc._packs[k]  # packed-weight variants of the losing candidates
-    p.out = real_out
-    AUTOTUNE_LOG.append(("%dx%d k%dx%d %d->%d out %dx%d" % (p.sy, p.sx, pc.kh, pc.kw, pc.cin, pc.cout, p.Hout, p.Wout),
-                         default, None if t_default is None else t_default * 1e3, best, best_t * 1e3))
-    return (best, best_t) if with_time else best
+    return _time_cfgs(lib, p, pc, cands, lambda c: _set_cfg(p, c, pc), "%dx%d k%dx%d %d->%d out %dx%d" % (
+        p.sy, p.sx, pc.kh, pc.kw, pc.cin, pc.cout, p.Hout, p.Wout))
 
 
 # ---------------------------------------------------------------------------- rolling-window convolutions
@@ -1006,10 +1020,6 @@ def _autotune(lib, p, pc, default, with_time=False):
 # least ROLL_MIN_PIXELS pixels (below that a 64-column strip grid cannot fill the chip and the tile kernels win).
 USE_ROLL = True
 ROLL_MIN_PIXELS = 2 * 288 * 480
-ROLL_RH = 0  # dev override of the rows per workgroup
-
-
-ROLL_C32 = False  # (dev: the 32-channel instantiations lose to the tile kernels)
 
 
 def use_roll(C, B, Cin_unused, H, W):
@@ -1018,7 +1028,7 @@ def use_roll(C, B, Cin_unused, H, W):
     few 64-column strips on HITNet's half-resolution maps to fill 256 CUs and stays on the tile kernels.  The kernel is
     exact fp32: under the plain bf16 mode (bf16 operands EVERYWHERE, BASELINE.json configs[4]) the layers stay on the bf16
     tile kernels so that the mode's dtype description holds."""
-    return (USE_ROLL and CONV_PRECISION in ("split", "split16", "fp32") and (C == 16 or (C == 32 and ROLL_C32))
+    return (USE_ROLL and CONV_PRECISION in ("split", "split16", "fp32") and C == 16
             and B * H * W >= ROLL_MIN_PIXELS)
 
 
@@ -1066,8 +1076,6 @@ class PackedRoll:
 def _roll_rh(B, H, W, mode):
     """Output rows per workgroup: the largest row block that still gives every CU ~3 workgroups (the strips of a
     launch are independent; a row block re-reads `lag` rows of its neighbour and idles for the pipeline fill)."""
-    if ROLL_RH:
-        return ROLL_RH
     stride = 60 if mode == 1 else 62
     strips = -(-W // stride) * B
     want = 3 * 256
@@ -1221,76 +1229,45 @@ def allpairs_corr_split(f1, f2):
             # the timing may only choose among configurations that give THE SAME BITS (tile shape and wave grid do not
             # change a sum, the chunk depth does): a pick that depended on the box would make the pyramid -- and with it
             # every selection downstream -- differ from lease to lease
-            if any(c[2] == 32 for c in ok):
-                ok = [c for c in ok if c[2] == 32]
+            if any(decode_cfg(c).ck == 32 for c in ok):
+                ok = [c for c in ok if decode_cfg(c).ck == 32]
             cfg = _allpairs_tune(lib, p, ok, f1[0], N, D) if tune else ok[0]
             if tune:
                 _ALLPAIRS_PICK[key] = cfg  # (un-tuned picks are not remembered: a later eager call may still time them)
-        xs = split_input_as(src, "split", cands=[cfg], p=p)
+        f = decode_cfg(cfg)
+        xs = _make_split(lib, p, src, None, [cfg], B=B)
         for b in range(B):
-            pk = (cfg[3], cfg[2])
-            if (pk, b) not in packs:  # weights[co = n1][ci = d] = f1[b, d, n1] / 16 for this (mb, ck)
-                nbytes = lib.codd_conv2d_packed_bytes_bf16(N, D, 1, 1, cfg[3], cfg[2], p.terms)
-                wp = torch.empty(nbytes, device=f1.device, dtype=torch.uint8)
-                _abi.check(lib.codd_conv2d_pack_weights_bf16(f1[b].data_ptr(), wp.data_ptr(), N, D, 1, 1, cfg[3], cfg[2], p.terms,
-                                                             1, N, 1.0 / 16.0, _stream()), "pack_weights_bf16")
-                packs[(pk, b)] = wp
-            p.wpacked = packs[(pk, b)].data_ptr()
+            if (f.mb, f.ck, b) not in packs:  # weights[co = n1][ci = d] = f1[b, d, n1] / 16 for this (mb, ck)
+                packs[(f.mb, f.ck, b)] = _pack_bf16(f1[b], N, D, 1, 1, f.mb, f.ck, p.terms, 1, N, 1.0 / 16.0)
+            p.wpacked = packs[(f.mb, f.ck, b)].data_ptr()
             p.out = lv[i][b].data_ptr()
             p.xs = xs.buf.data_ptr() + b * (xs.buf.numel() // B)
-            p.xs_c8, p.xs_hp, p.xs_wp, p.xs_bt, p.xs_bl, p.xs_o8 = xs.c8, xs.hp, xs.wp, xs.bt, xs.bl, 0
-            p.npb, p.nw, p.ck, p.mb, p.layout, p.pgw, p.cgw = cfg[:7]
-            p.ksplit = cfg[8]
+            _set_cfg(p, cfg)
             _abi.check(_launch_conv(lib, p, _stream()), "allpairs conv")
     return lv
 
 
-def split_input_as(x, mode, cands, p):
-    """codd_split_bf16 of ``x`` (3 terms) sized for the configurations ``cands`` of the conv described by ``p``."""
-    lib = _abi.load()
-    c8, hp, wp = _split_dims(p, cands)
-    B, C0, H, W = x.shape
-    t = p.terms if p.terms in (3, 48) else 3
-    buf = torch.empty(lib.codd_split_bf16_bytes(B, c8, hp, wp, t), device=x.device, dtype=torch.uint8)
-    _abi.check(lib.codd_split_bf16(_view(x), C0, _view(None), 0, B, H, W, 0, 0, c8, hp, wp, t, buf.data_ptr(), _stream()),
-               "codd_split_bf16")
-    return SplitTensor(buf, B, C0, H, W, 0, 0, hp, wp, c8, t)
-
-
 def _allpairs_tune(lib, p, cands, f1b, N, D):
-    """Time the accepted all-pairs configurations on this level's shape (own split input / weights per candidate)."""
-    best, best_t = cands[0], float("inf")
+    """Time the accepted all-pairs configurations on this level's shape (_time_cfgs; own split input / weights per
+    candidate)."""
     src = torch.zeros(1, D, p.Hin, p.Win, device=f1b.device)
-    for c in cands:
-        xs = split_input_as(src, "split", [c], p)
-        nbytes = lib.codd_conv2d_packed_bytes_bf16(N, D, 1, 1, c[3], c[2], p.terms)
-        wp = torch.empty(nbytes, device=f1b.device, dtype=torch.uint8)
-        lib.codd_conv2d_pack_weights_bf16(f1b.data_ptr(), wp.data_ptr(), N, D, 1, 1, c[3], c[2], p.terms, 1, N, 1.0 / 16.0, _stream())
-        p.wpacked, p.xs = wp.data_ptr(), xs.buf.data_ptr()
-        p.xs_c8, p.xs_hp, p.xs_wp, p.xs_bt, p.xs_bl, p.xs_o8 = xs.c8, xs.hp, xs.wp, xs.bt, xs.bl, 0
-        p.npb, p.nw, p.ck, p.mb, p.layout, p.pgw, p.cgw = c[:7]
-        p.ksplit = c[8]
-        if lib.codd_conv2d(C.byref(p), _stream()) != 0:
-            continue
-        torch.cuda.synchronize()
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        for _ in range(3):
-            lib.codd_conv2d(C.byref(p), _stream())
-        e.record()
-        e.synchronize()
-        t = s.elapsed_time(e) / 3
-        if t < best_t * 0.97:
-            best, best_t = c, t
-    AUTOTUNE_LOG.append(("allpairs %dx%d" % (p.Hin, p.Win), cands[0], None, best, best_t * 1e3))
-    return best
+
+    def apply(c):
+        f = decode_cfg(c)
+        xs = _make_split(lib, p, src, None, [c])
+        wp = _pack_bf16(f1b, N, D, 1, 1, f.mb, f.ck, p.terms, 1, N, 1.0 / 16.0)
+        p.wpacked = wp.data_ptr()
+        _set_cfg(p, c)
+        return xs, wp
+
+    return _time_cfgs(lib, p, None, cands, apply, "allpairs %dx%d" % (p.Hin, p.Win))[0]
 
 
 def allpairs_corr(f1, f2, split=None):
     """-> 4 pyramid levels [B, h*w, (h>>i)*(w>>i)] (reference blocks/corr.py:28-45).  ``split`` (default: the "split"
     conv precision is active): the GEMMs run on the split-bf16 kernel (allpairs_corr_split), else on exact-fp32 MFMA."""
     if split is None:
-        split = CONV_PRECISION in _SPLIT_MODES and ALLPAIRS_SPLIT
+        split = CONV_PRECISION in _SPLIT_MODES
     if split:
         return allpairs_corr_split(f1, f2)
     lib = _abi.load()

@@ -6,7 +6,7 @@ of every variant against the default product path, and of every variant against 
 (tests/golden/headline_oracle_long_sub4.npz).  If product-vs-product drifts like product-vs-oracle, the drift is a
 property of the recurrence (discontinuous selections fed back through state["memory"]), not of an implementation.
 """
-import os, sys
+import functools, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np
@@ -44,9 +44,10 @@ def run(tag, roll=True, precision="split", noise=0.0, graph=True, exact=()):
         elif what == "update": r3.update_block.run = _fp32(r3.update_block.run)
         elif what == "fusion": est.fusion.memory_query = _fp32(est.fusion.memory_query)
         elif what == "motion": est.motion.forward = _fp32(est.motion.forward)
-    prev_roll, prev_p, prev_ap = ops.USE_ROLL, ops.set_conv_precision(precision), ops.ALLPAIRS_SPLIT
+    prev_roll, prev_p, prev_ap = ops.USE_ROLL, ops.set_conv_precision(precision), ops.allpairs_corr
     ops.USE_ROLL = roll
-    ops.ALLPAIRS_SPLIT = prev_ap and "allpairs" not in exact
+    if "allpairs" in exact:  # the all-pairs GEMMs on the exact-fp32 kernel
+        ops.allpairs_corr = functools.partial(prev_ap, split=False)
     ops.enable_autotune(True, shipped=True)
     out = []
     try:
@@ -61,7 +62,7 @@ def run(tag, roll=True, precision="split", noise=0.0, graph=True, exact=()):
     finally:
         ops.enable_autotune(False)
         ops.USE_ROLL = prev_roll
-        ops.ALLPAIRS_SPLIT = prev_ap
+        ops.allpairs_corr = prev_ap
         ops.set_conv_precision(prev_p)
     return out
 

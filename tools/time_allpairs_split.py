@@ -28,14 +28,9 @@ for pgw, cgw, a, b, ks in ops._B_INST:
             p.terms, p.out_ctot = 3, N
             if not ops._cfg_ok(lib, p, c):
                 continue
-            xs = ops.split_input_as(f2, "split", [c], p)
-            nb = lib.codd_conv2d_packed_bytes_bf16(N, D, 1, 1, mb, ck, 3)
-            wp = torch.empty(nb, device="cuda", dtype=torch.uint8)
-            lib.codd_conv2d_pack_weights_bf16(f1.data_ptr(), wp.data_ptr(), N, D, 1, 1, mb, ck, 3, 1, N, 1.0 / 16.0, None)
-            p.wpacked, p.xs, p.out = wp.data_ptr(), xs.buf.data_ptr(), out.data_ptr()
-            p.xs_c8, p.xs_hp, p.xs_wp, p.xs_bt, p.xs_bl, p.xs_o8 = xs.c8, xs.hp, xs.wp, 0, 0, 0
-            p.npb, p.nw, p.ck, p.mb, p.layout, p.pgw, p.cgw = c[:7]
-            p.ksplit = ks
+            xs = ops._make_split(lib, p, f2, None, [c])  # noqa: F841 (attached to p)
+            wp = ops._pack_bf16(f1[0], N, D, 1, 1, mb, ck, 3, 1, N, 1.0 / 16.0)
+            p.wpacked, p.out = wp.data_ptr(), out.data_ptr()
             if lib.codd_conv2d(C.byref(p), None) != 0:
                 continue
             torch.cuda.synchronize()

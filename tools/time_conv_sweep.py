@@ -25,9 +25,8 @@ for cin, cout, k, dil in shapes:
     ref = None
     line = f"{cin:4d}->{cout:4d} k{k} d{dil}:"
     for mb in ((2, 4) if cout <= 128 else (4,)):
-        os.environ["CODD_MB"] = str(mb)
-        ops._FORCE_MB = mb if hasattr(ops, "_FORCE_MB") else None
         pc = ops.PackedConv(wt, torch.zeros(cout, device=dev))
+        pc.mb = mb  # 16-channel blocks per workgroup of the heuristic configuration
         for nw in (4, 9):
             ops._FORCE_NW = nw
             try:
