@@ -119,6 +119,8 @@ SIGNATURES = {
     "codd_sceneflow_metrics": (_i, [_p] * 6 + [_i] * 5 + [_f] * 7 + [_p, _p, _p]),
     "codd_preprocess": (_i, [_p, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _p, _p]),
     "codd_fusion_blend": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "codd_ingest_pair": (_i, [_p, _p, _i, _i, _i, c_float_p, c_float_p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
+    "codd_export_depth": (_i, [_p, _i, _i, _i, _i, _i, _f, _p, _p]),
 }
 
 ABI_VERSION = 12  # CODD_ABI_VERSION of include/codd_hip.h

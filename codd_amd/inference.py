@@ -36,6 +36,10 @@ def parse_args(argv=None):
     p.add_argument("--launcher", choices=["none", "pytorch"], default="none")
     p.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay of the frame")
     p.add_argument("--no-autotune", action="store_true", help="static launch heuristics (bit-reproducible runs)")
+    p.add_argument("--live", action="store_true", help="feed each video frame by frame through a codd_amd.live.LiveSession "
+                   "(no --num-frames cap, no whole-clip tensor: host memory does not grow with the video)")
+    p.add_argument("--output", choices=["disp", "depth", "disp_u16"], default="disp", help="--live: what is written")
+    p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
     return p.parse_args(argv)
 
 
@@ -82,6 +86,80 @@ def make_sample(name, lefts, rights, device, num_frames=-1, disp_paths=None):
     return data
 
 
+def iter_frames(lefts, rights):
+    """(left, right) uint8 RGB [h,w,3] pairs in the order given, each decoded only when asked for."""
+    from PIL import Image
+    for lp, rp in zip(lefts, rights):
+        yield tuple(np.ascontiguousarray(np.array(Image.open(p).convert("RGB"))) for p in (lp, rp))
+
+
+def live_results(session, frames, depth=2):
+    """Push ``frames`` through ``session`` keeping at most ``depth`` of them in flight; yields the results in order."""
+    frames = iter(frames)
+    while True:
+        if session.pending() >= depth:  # (before the next frame is decoded: never more than ``depth`` frames alive)
+            yield session.pop()
+        pair = next(frames, None)
+        if pair is None:
+            break
+        session.push(*pair)
+    while session.pending():
+        yield session.pop()
+
+
+class _NpzStream:
+    """Writes ``<key>.npy`` of a known shape into a compressed .npz one frame at a time (what np.savez_compressed
+    writes, without holding the whole array)."""
+
+    def __init__(self, path, key, shape, dtype):
+        import zipfile
+        self.zip = zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, allowZip64=True)
+        self.f = self.zip.open(key + ".npy", "w", force_zip64=True)
+        np.lib.format.write_array_header_1_0(self.f, dict(descr=np.lib.format.dtype_to_descr(np.dtype(dtype)),
+                                                          fortran_order=False, shape=tuple(shape)))
+
+    def write(self, a):
+        self.f.write(np.ascontiguousarray(a).tobytes())
+
+    def close(self):
+        self.f.close()
+        self.zip.close()
+
+
+def run_live(args, model, videos):
+    """--live: one LiveSession per frame size, every video pushed through it frame by frame; with --show each video's
+    results go to <show-dir>/<name>.disp.pred.npz ([1, frames, h, w], as the default path writes)."""
+    from PIL import Image
+    from .live import LiveSession
+    maps = None
+    if args.rectify_maps:
+        z = np.load(args.rectify_maps)
+        maps = ((z["left_x"], z["left_y"]), (z["right_x"], z["right_y"]))
+    sessions = {}
+    for name, lefts, rights in videos:
+        w, h = Image.open(lefts[0]).size
+        s = sessions.get((h, w))
+        if s is None:
+            s = sessions[(h, w)] = LiveSession(model, (h, w), intrinsics=CUSTOM["intrinsics"], calib=CUSTOM["calib"],
+                                               output=args.output, bgr=False, rectify=maps, use_graph=not args.no_graph)
+        s.reset()
+        out = None
+        if args.show:
+            os.makedirs(args.show_dir, exist_ok=True)
+            out = _NpzStream(osp.join(args.show_dir, name + ".disp.pred.npz"), "disp", (1, len(lefts), h, w),
+                             np.uint16 if args.output == "disp_u16" else np.float32)
+        n = 0
+        for res in live_results(s, iter_frames(lefts, rights)):
+            n += 1
+            if out is not None:
+                out.write(res)
+        if out is not None:
+            out.close()
+        print(f"{name}: {n} frames")
+    for s in sessions.values():
+        s.close()
+
+
 def main(argv=None):
     args = parse_args(argv)
     distributed = args.launcher != "none"
@@ -102,6 +180,15 @@ def main(argv=None):
     ops.enable_autotune(not args.no_autotune)  # time the conv launch configurations once per layer shape
     videos = list_videos(args.img_dir, args.r_img_dir, args.img_suffix)
     mine = apis.shard_loader(videos) if distributed else videos
+    if args.live:
+        assert not args.eval, "--live writes results (--show); metrics need the default path"
+        with torch.no_grad():
+            run_live(args, model, mine)
+        if distributed:
+            import torch.distributed as dist
+            dist.barrier()
+            dist.destroy_process_group()
+        return None
 
     def loader():
         for name, lf, rf in mine:

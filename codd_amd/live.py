@@ -1,0 +1,211 @@
+"""Live stereo session: host ``uint8`` camera frames in, host depth maps out, one frame at a time.
+
+The reference has no online entry: datasets/custom_stereo_mf.py cuts a video into multi-frame samples and
+model/codd.py:290-398 walks a whole resident clip.  ``LiveSession`` owns everything between a frame in host memory
+and a result the caller may keep, around the FrameRunner's captured frame graph:
+
+    pinned host slot --(copy stream)--> device uint8 slot --codd_ingest_pair--> the graph's own static inputs
+    --graph replay--> padded disparity --codd_export_depth--> device staging --(copy stream)--> pinned host slot
+
+Ingest and export run on the compute stream, outside the graph, right before and after the replay; both copies run on
+streams of their own, ordered against the compute stream with events, so the upload of frame t+1 and the download of
+frame t-1 overlap the compute of frame t.  Every buffer is allocated once, at the first frame.
+"""
+from collections import deque
+
+import numpy as np
+import torch
+
+from . import _abi, ops, synth
+from .runtime import FrameRunner
+
+OUTPUTS = ("disp", "depth", "disp_u16")
+DEPTH = 2  # frames in flight: input, device and host output slots are double-buffered
+
+
+def check_frame(a, shape, name="frame"):
+    """A C-contiguous uint8 [h,w,3] numpy array or CPU tensor, else TypeError / ValueError (no device call)."""
+    if isinstance(a, torch.Tensor):
+        if a.is_cuda:
+            raise TypeError(f"{name}: a host (CPU) tensor is expected, got one on {a.device}")
+        dtype_ok, contiguous, shp = a.dtype == torch.uint8, a.is_contiguous(), tuple(a.shape)
+    elif isinstance(a, np.ndarray):
+        dtype_ok, contiguous, shp = a.dtype == np.uint8, a.flags["C_CONTIGUOUS"], tuple(a.shape)
+    else:
+        raise TypeError(f"{name}: numpy array or CPU tensor expected, got {type(a).__name__}")
+    if not dtype_ok:
+        raise ValueError(f"{name}: dtype uint8 expected, got {a.dtype}")
+    if shp != (shape[0], shape[1], 3):
+        raise ValueError(f"{name}: shape {(shape[0], shape[1], 3)} expected, got {shp}")
+    if not contiguous:
+        raise ValueError(f"{name}: a C-contiguous array is expected")
+    return a
+
+
+def _check_maps(rectify, shape):
+    if rectify is None:
+        return None
+    if len(rectify) != 2:
+        raise ValueError("rectify: ((left_x, left_y), (right_x, right_y)) expected")
+    out = []
+    for view, pair in zip(("left", "right"), rectify):
+        if pair is None:
+            out.append(None)
+            continue
+        if len(pair) != 2 or pair[0] is None or pair[1] is None:
+            raise ValueError(f"rectify: the {view} view needs both map_x and map_y")
+        maps = []
+        for m in pair:
+            m = np.ascontiguousarray(m, dtype=np.float32)
+            if m.shape != tuple(shape):
+                raise ValueError(f"rectify: {view} map of shape {m.shape}, expected {tuple(shape)}")
+            maps.append(m)
+        out.append(tuple(maps))
+    return tuple(out)
+
+
+class LiveSession:
+    """``step(left, right)`` is synchronous; ``push`` / ``pop`` pipeline two frames.
+
+    Ownership: ``push`` copies both images into the session's pinned slots before it returns, so the caller may reuse
+    its arrays at once; every result is a fresh numpy array owned by the caller.  At most ``DEPTH`` (2) frames are in
+    flight: a further ``push`` first waits for the OLDEST frame's download and parks its result in an internal queue,
+    which ``pop`` drains first -- results always come out in push order and no slot in flight is overwritten.
+    """
+
+    def __init__(self, estimator, shape, intrinsics=(1050.0, 1050.0, 480.0, 270.0), calib=210.0, output="depth",
+                 bgr=False, rectify=None, use_graph=True, divisor=64):
+        if output not in OUTPUTS:
+            raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
+        h, w = int(shape[0]), int(shape[1])
+        if h <= 0 or w <= 0:
+            raise ValueError(f"shape: positive (h, w) expected, got {shape}")
+        self.est, self.shape, self.output, self.bgr, self.calib = estimator, (h, w), output, bool(bgr), float(calib)
+        self.padded = (-(-h // divisor) * divisor, -(-w // divisor) * divisor)
+        self._maps_host = _check_maps(rectify, (h, w))
+        # one sample's img_metas (the list the estimator's inference() is handed): [dict]
+        self.metas = synth.default_metas(*self.padded, img_shape=(h, w, 3), intrinsics=tuple(intrinsics))[0]
+        self.metas[0]["calib"] = self.calib
+        self.runner = FrameRunner(estimator, self.metas, use_graph=use_graph)
+        self._open_done = False
+        self._pushed = 0
+        self._inflight = deque()  # slots, oldest first
+        self._ready = deque()  # results popped on the caller's behalf by a push that found the pipeline full
+
+    # ---- one-time allocation ------------------------------------------------------------------------
+    def _open(self):
+        dev = next(self.est.parameters()).device
+        if dev.type != "cuda":
+            raise _abi.CoddHipError("LiveSession needs an estimator on a ROCm device (no CPU fallback in the product path)")
+        _abi.load()
+        h, w = self.shape
+        H, W = self.padded
+        self.dev = dev
+        odt = torch.int16 if self.output == "disp_u16" else torch.float32  # (uint16 bits; handed out as numpy uint16)
+        with torch.cuda.device(dev):
+            self._h_in = [[torch.empty(h, w, 3, dtype=torch.uint8, pin_memory=True) for _ in range(2)] for _ in range(DEPTH)]
+            self._d_in = [[torch.empty(h, w, 3, dtype=torch.uint8, device=dev) for _ in range(2)] for _ in range(DEPTH)]
+            self._scratch = tuple(torch.empty(1, 3, H, W, dtype=torch.float32, device=dev) for _ in range(2))
+            self._maps = None
+            if self._maps_host is not None:
+                self._maps = tuple(None if p is None else tuple(torch.from_numpy(m).to(dev) for m in p)
+                                   for p in self._maps_host)
+            self._d_out = torch.empty(h, w, dtype=odt, device=dev)
+            self._h_out = [torch.empty(h, w, dtype=odt, pin_memory=True) for _ in range(DEPTH)]
+            self._s_up, self._s_down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+            ev = lambda: [torch.cuda.Event() for _ in range(DEPTH)]  # noqa: E731
+            self._e_up, self._e_ingest, self._e_export, self._e_down = ev(), ev(), ev(), ev()
+        self._open_done = True
+
+    # ---- pipeline -----------------------------------------------------------------------------------
+    def push(self, left_u8, right_u8):
+        """Enqueue one frame.  Returns once both images sit in the session's pinned slot."""
+        check_frame(left_u8, self.shape, "left")
+        check_frame(right_u8, self.shape, "right")
+        if not self._open_done:
+            self._open()
+        if len(self._inflight) == DEPTH:
+            self._ready.append(self._collect())
+        k = self._pushed % DEPTH
+        first_use = self._pushed < DEPTH
+        if not first_use:
+            self._e_up[k].synchronize()  # the slot's previous upload has left the pinned memory
+        with torch.cuda.device(self.dev), torch.no_grad():
+            compute = torch.cuda.current_stream(self.dev)
+            with torch.cuda.stream(self._s_up):
+                if not first_use:
+                    self._s_up.wait_event(self._e_ingest[k])  # the slot's previous frame has been read by its ingest
+                # view by view: the left image's upload runs while the host copies the right one into its slot
+                for dev_slot, host_slot, src in zip(self._d_in[k], self._h_in[k], (left_u8, right_u8)):
+                    if isinstance(src, torch.Tensor):
+                        host_slot.copy_(src)
+                    else:
+                        np.copyto(host_slot.numpy(), src)
+                    dev_slot.copy_(host_slot, non_blocking=True)
+                self._e_up[k].record(self._s_up)
+            compute.wait_event(self._e_up[k])
+
+            def fill(left, right):
+                ops.ingest_pair(self._d_in[k][0], self._d_in[k][1], left, right, bgr=self.bgr, maps=self._maps)
+                self._e_ingest[k].record(compute)
+
+            disp = self.runner.step_fill(fill, self._scratch)
+            if self._pushed > 0:
+                compute.wait_event(self._e_down[(self._pushed - 1) % DEPTH])  # one device staging buffer
+            ops.export_depth(disp, self._d_out, mode=self.output, calib=self.calib)
+            self._e_export[k].record(compute)
+            with torch.cuda.stream(self._s_down):
+                self._s_down.wait_event(self._e_export[k])
+                self._h_out[k].copy_(self._d_out, non_blocking=True)
+                self._e_down[k].record(self._s_down)
+        self._inflight.append(k)
+        self._pushed += 1
+
+    def _collect(self):
+        k = self._inflight.popleft()
+        self._e_down[k].synchronize()  # this frame's download only
+        res = self._h_out[k].numpy().copy()
+        return res.view(np.uint16) if self.output == "disp_u16" else res
+
+    def pop(self):
+        """The oldest frame's result: numpy [h,w] (fp32, or uint16 for ``disp_u16``), owned by the caller."""
+        if self._ready:
+            return self._ready.popleft()
+        if not self._inflight:
+            raise IndexError("pop from an empty LiveSession")
+        return self._collect()
+
+    def pending(self):
+        """Frames pushed and not yet popped (in flight or parked)."""
+        return len(self._ready) + len(self._inflight)
+
+    def step(self, left_u8, right_u8):
+        """One frame, synchronously (any frames already pushed are returned first by ``pop``, so drain them before)."""
+        if self.pending():
+            raise RuntimeError("step() on a session with frames in flight: pop() them first")
+        self.push(left_u8, right_u8)
+        return self.pop()
+
+    def reset(self):
+        """New sequence (reference reset_inference_state, model/codd.py:400-433).  Frames in flight stay poppable; the
+        captured graph is kept."""
+        self.runner.reset()
+        self.est.reset_inference_state()
+
+    def close(self):
+        if self._open_done:
+            self._s_up.synchronize()
+            torch.cuda.current_stream(self.dev).synchronize()
+            self._s_down.synchronize()
+            for name in ("_h_in", "_d_in", "_scratch", "_maps", "_d_out", "_h_out"):
+                setattr(self, name, None)
+            self._open_done = False
+        self._inflight.clear()
+        self._ready.clear()
+        self.runner = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

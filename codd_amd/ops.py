@@ -1723,6 +1723,48 @@ def preprocess(img_u8, bgr=True, mean=IMAGENET_MEAN, std=IMAGENET_STD, divisor=6
     return out
 
 
+def ingest_pair(left_u8, right_u8, out_left, out_right, bgr=True, maps=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """Both views of one frame in one launch: uint8 [h,w,3] device images -> normalised, reflect-padded fp32 written
+    into the caller's [..,3,H,W] buffers (nothing is allocated).  ``maps``: None or ((lmx, lmy), (rmx, rmy)), fp32
+    [h,w] device rectification maps per view (either pair may be None).  Without maps the result is bit-identical to
+    ``preprocess`` of each view."""
+    lib = _abi.load()
+    _require_gpu(left_u8)
+    h, w = left_u8.shape[:2]
+    for t in (left_u8, right_u8):
+        assert t.dtype == torch.uint8 and tuple(t.shape) == (h, w, 3) and t.is_contiguous() and t.is_cuda
+    H, W = out_left.shape[-2:]
+    for t in (out_left, out_right):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and t.numel() == 3 * H * W
+    ptrs = []
+    for pair in (maps or (None, None)):
+        for m in (pair or (None, None)):
+            if m is not None:
+                assert m.dtype == torch.float32 and tuple(m.shape) == (h, w) and m.is_contiguous() and m.is_cuda
+            ptrs.append(None if m is None else m.data_ptr())
+    m, s = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    _abi.check(lib.codd_ingest_pair(left_u8.data_ptr(), right_u8.data_ptr(), h, w, int(bgr), m, s, *ptrs, H, W,
+                                    out_left.data_ptr(), out_right.data_ptr(), _stream()), "ingest_pair")
+
+
+EXPORT_MODES = dict(disp=0, depth=1, disp_u16=2)  # CODD_EXPORT_* of include/codd_hip.h
+
+
+def export_depth(disp, out, mode="disp", calib=1.0):
+    """The frame's padded disparity [1,1,H,W] -> the cropped [h,w] result in ``out`` (fp32, or uint16 for
+    ``disp_u16``; caller-owned device staging buffer).  ``depth`` is calib / disp."""
+    lib = _abi.load()
+    _require_gpu(disp)
+    H, W = disp.shape[-2:]
+    h, w = out.shape
+    assert disp.dtype == torch.float32 and disp.is_contiguous() and disp.numel() == H * W
+    # (uint16 results may live in an int16 tensor: same bytes, and every torch build copies int16)
+    assert out.is_cuda and out.is_contiguous() and out.dtype in ((torch.uint16, torch.int16) if mode == "disp_u16" else (torch.float32,))
+    _abi.check(lib.codd_export_depth(disp.data_ptr(), H, W, h, w, EXPORT_MODES[mode], float(calib), out.data_ptr(),
+                                     _stream()), "export_depth")
+    return out
+
+
 def fusion_select(mode, cur, warp, gt=None, K=0.5):
     """mode 'kalman' / 'gt' (ablation fusions).  cur, warp [B,1,H,W]; gt [B,1,hg,wg]."""
     lib = _abi.load()

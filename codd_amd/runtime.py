@@ -116,6 +116,29 @@ class FrameRunner:
         torch.cuda.current_stream(dev).wait_stream(stream)
         self.graph, self._static = g, st
 
+    def step_fill(self, fill, scratch):
+        """One frame whose inputs the caller writes in place: ``fill(left, right)`` must enqueue, on the current
+        stream, the writes of this frame's normalised images into the two [B,3,H,W] buffers it is given.  Once the
+        frame graph is live those are the graph's own static inputs, so the frame costs no device-to-device copy
+        (codd_amd.live feeds camera frames this way); until then (the eager first frame, the capturing second one,
+        the re-priming frame after reset()) they are ``scratch = (left, right)``, the caller's own buffers, and the
+        frame goes through ``step`` unchanged.  Same result and same validity as ``step``."""
+        st = self._static
+        stateless = self.est.motion is None and self.est.fusion is None
+        if not self.use_graph or self.graph is None or not (stateless or st["primed"]):
+            fill(*scratch)
+            return self.step(*scratch)
+        self.frames += 1
+        fill(st["l"], st["r"])
+        self.graph.replay()
+        if stateless:
+            return st["out"]
+        self.state = {"memory": True}
+        self.last = st.get("last", {})
+        if self.check_finite and not bool(torch.isfinite(st["out"]).all()):
+            raise FloatingPointError(f"frame {self.frames}: non-finite disparity (conv precision {ops.CONV_PRECISION})")
+        return st["out"]
+
     def step(self, left, right):
         """One frame.  Returns the (fused) disparity [B,1,H,W]; valid until the next call."""
         self.frames += 1

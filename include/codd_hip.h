@@ -494,6 +494,38 @@ int codd_sceneflow_metrics(const float* Ts, const float* pred_prev, const float*
 int codd_preprocess(const unsigned char* img, int h, int w, int bgr, const float* mean, const float* stdv,
                     int H, int W, float* out, void* stream);
 
+/* Live-session ingest (codd_amd/live.py): BOTH views of one frame in one launch.  Replaces, per camera frame, the two
+ * Pad + Normalize + format passes of the reference's test pipeline (datasets/transforms.py:147-161, 373-427;
+ * datasets/formating.py:65-85, run on img and r_img by datasets/custom_stereo_mf.py) and the host cv2.remap a user
+ * of the reference runs in front of them on an unrectified rig.
+ *   left, right   uint8 [h,w,3] HWC (device); out_left, out_right fp32 [3,H,W] (device, caller-owned: no allocation);
+ *   mean / stdv   host pointers to 3 floats in RGB order; bgr != 0: the source is BGR.
+ * Without maps (all four NULL) each output is bit-identical to codd_preprocess() of that view.
+ * With maps (map_x, map_y: fp32 [h,w] per view, device, the layout cv2.initUndistortRectifyMap produces; a view's two
+ * maps are given together or not at all, each view independently), pixel (y,x) of the rectified h x w image is the
+ * bilinear sample of the source at (sx, sy) = (map_x[y,x], map_y[y,x]):
+ *   x0 = floor(sx), y0 = floor(sy); weights ax = sx - x0, ay = sy - y0 computed in fp32;
+ *   a tap outside the source contributes 0 in raw uint8 units; a non-finite map entry gives 0;
+ *   v = (v00*(1-ax) + v01*ax)*(1-ay) + (v10*(1-ax) + v11*ax)*ay in fp32, NOT rounded back to uint8; then (v - mean)/std.
+ * The padded border is the BORDER_REFLECT_101 reflection of the RECTIFIED image.  An identity map gives the bits of the
+ * map-free path.  Same size rules as codd_preprocess: h <= H < 2h, w <= W < 2w. */
+int codd_ingest_pair(const unsigned char* left, const unsigned char* right, int h, int w, int bgr, const float* mean,
+                     const float* stdv, const float* lmap_x, const float* lmap_y, const float* rmap_x,
+                     const float* rmap_y, int H, int W, float* out_left, float* out_right, void* stream);
+
+/* Live-session export: the frame's padded disparity [1,1,H,W] -> the cropped h x w result, contiguous, in a
+ * caller-owned device staging buffer (model/codd.py:370-377: `calib / pred_disp` under reciprocal, then the
+ * [:img_h, :img_w] crop).  mode:
+ *   CODD_EXPORT_DISP      fp32 disparity (crop only);
+ *   CODD_EXPORT_DEPTH     fp32 depth calib * (1 / disp): torch evaluates `calib / disp` with a Python scalar on top as
+ *                         disp.reciprocal() * calib, so these are the bits inference(reciprocal=True) returns;
+ *   CODD_EXPORT_DISP_U16  uint16 round-to-nearest-even(disp * 256) clamped to [0, 65535], non-finite -> 0 (the KITTI
+ *                         devkit's PNG convention). */
+#define CODD_EXPORT_DISP 0
+#define CODD_EXPORT_DEPTH 1
+#define CODD_EXPORT_DISP_U16 2
+int codd_export_depth(const float* disp, int H, int W, int h, int w, int mode, float calib, void* out, void* stream);
+
 /* Ablation plug-ins.  codd_fusion_select: mode 0 = KalmanFusion (model/fusion/others.py:124-153; constant
  * gain K = Q/(Q+R), the reference never updates P), mode 1 = GTFusion (:54-86; gt [B,1,hg,wg], zero-padded).
  * cur, warp, out: [B,1,H,W]. */
