@@ -355,6 +355,9 @@ extern "C" int codd_raft_geometry_lookup_xs(const float* T, const float* depth1,
 // Per-iteration geometry (reference raft3d.py:225-240).
 // ------------------------------------------------------------------------------------------------
 
+// the +-50 clamp of the motion-info channels with torch.clamp's semantics: a NaN stays a NaN (fmaxf(NaN, -50) is -50)
+__device__ __forceinline__ float clamp50(float v) { return v != v ? v : fminf(fmaxf(v, -50.f), 50.f); }
+
 // full per-pixel geometry of pixel n (batch b): writes xyz[n] and the 9 motion-info channels
 __device__ __forceinline__ void raft_geometry_pixel(const float* __restrict__ T, const float* __restrict__ d1,
                                                     const float* __restrict__ d2, int b, int pix, int h, int w,
@@ -389,15 +392,15 @@ __device__ __forceinline__ void raft_geometry_pixel(const float* __restrict__ T,
   if (mxs) {  // the 9 channels as split-bf16 records: octet 0 and slot 0 of octet 1 (the other 7 slots stay zero)
     float v0[8], v1[8];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) { v0[c] = fminf(fmaxf(vals[c], -50.f), 50.f); v1[c] = 0.f; }
-    v1[0] = fminf(fmaxf(vals[8], -50.f), 50.f);
+    for (int c = 0; c < 8; ++c) { v0[c] = clamp50(vals[c]); v1[c] = 0.f; }
+    v1[0] = clamp50(vals[8]);
     xs_store8(*mxs, b, 0, y, x, v0);
     xs_store8(*mxs, b, 1, y, x, v1);
     return;
   }
   float* mp = minfo + (size_t)b * 9 * N + pix;
 #pragma unroll
-  for (int c = 0; c < 9; ++c) mp[(size_t)c * N] = fminf(fmaxf(vals[c], -50.f), 50.f);
+  for (int c = 0; c < 9; ++c) mp[(size_t)c * N] = clamp50(vals[c]);
 }
 
 __global__ void raft_geometry_kernel(const float* __restrict__ T, const float* __restrict__ d1,
