@@ -17,17 +17,21 @@ int codd_opt(int key);  // current value of a CODD_OPT_* option (stereo.hip)
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// ReLU with torch.relu's semantics: a NaN stays a NaN (fmaxf(NaN, 0) is 0, which would hide an inf - inf upstream from
+// every finite check downstream).  No finite input changes a bit.
+__device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
 __device__ __forceinline__ float act_apply(float v, int act, int co) {
   switch (act) {
     case CODD_ACT_LRELU02: return v > 0.f ? v : 0.2f * v;
-    case CODD_ACT_RELU: return fmaxf(v, 0.f);
+    case CODD_ACT_RELU: return relu_nan(v);
     case CODD_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
     case CODD_ACT_TANH: return tanhf(v);
     case CODD_ACT_MISH: {
       float sp = v > 20.f ? v : log1pf(expf(v));
       return v * tanhf(sp);
     }
-    case CODD_ACT_RELU_CH0: return co == 0 ? fmaxf(v, 0.f) : v;
+    case CODD_ACT_RELU_CH0: return co == 0 ? relu_nan(v) : v;
     default: return v;
   }
 }

@@ -182,7 +182,7 @@ __device__ __forceinline__ f32x4 convb_act(f32x4 v, int act, int co) {
   if (act == CODD_ACT_NONE) return v;
   if (act == CODD_ACT_RELU || (act == CODD_ACT_RELU_CH0 && co == 0)) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+    for (int r = 0; r < 4; ++r) v[r] = relu_nan(v[r]);
     return v;
   }
   if (act == CODD_ACT_RELU_CH0) return v;

@@ -34,7 +34,7 @@ namespace {
 // the activations HITNet uses (the generic act_apply carries exp / log / tanh code for every epilogue value)
 __device__ __forceinline__ float roll_act(float v, int act, int co) {
   if (act == CODD_ACT_LRELU02) return v > 0.f ? v : 0.2f * v;
-  if (act == CODD_ACT_RELU || (act == CODD_ACT_RELU_CH0 && co == 0)) return fmaxf(v, 0.f);
+  if (act == CODD_ACT_RELU || (act == CODD_ACT_RELU_CH0 && co == 0)) return relu_nan(v);
   return v;
 }
 
