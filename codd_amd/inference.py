@@ -39,8 +39,15 @@ def parse_args(argv=None):
     p.add_argument("--live", action="store_true", help="feed each video frame by frame through a codd_amd.live.LiveSession "
                    "(no --num-frames cap, no whole-clip tensor: host memory does not grow with the video)")
     p.add_argument("--output", choices=["disp", "depth", "disp_u16"], default="disp", help="--live: what is written")
+    p.add_argument("--motion", choices=["flow2d", "flow_dd", "sceneflow"], default=None,
+                   help="--live: also write <name>.motion.pred.npz, key motion, [1, frames, h, w, C] fp32: the per-pixel motion "
+                   "from the previous frame to this one on the previous frame's grid (flow2d: pixels; flow_dd: + disparity "
+                   "change; sceneflow: 3-D, in the unit of calib); NaN where invalid and in frames without a field")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.motion is not None and not args.live:
+        p.error("--motion needs --live")
+    return args
 
 
 def _natural(names):
@@ -128,7 +135,8 @@ class _NpzStream:
 
 def run_live(args, model, videos):
     """--live: one LiveSession per frame size, every video pushed through it frame by frame; with --show each video's
-    results go to <show-dir>/<name>.disp.pred.npz ([1, frames, h, w], as the default path writes)."""
+    results go to <show-dir>/<name>.disp.pred.npz ([1, frames, h, w], as the default path writes) and, with --motion,
+    <name>.motion.pred.npz ([1, frames, h, w, C]; a frame without a field is all NaN)."""
     from PIL import Image
     from .live import LiveSession
     maps = None
@@ -141,20 +149,30 @@ def run_live(args, model, videos):
         s = sessions.get((h, w))
         if s is None:
             s = sessions[(h, w)] = LiveSession(model, (h, w), intrinsics=CUSTOM["intrinsics"], calib=CUSTOM["calib"],
-                                               output=args.output, bgr=False, rectify=maps, use_graph=not args.no_graph)
+                                               output=args.output, bgr=False, rectify=maps, use_graph=not args.no_graph,
+                                               motion=args.motion)
         s.reset()
-        out = None
+        out = mot = None
         if args.show:
             os.makedirs(args.show_dir, exist_ok=True)
             out = _NpzStream(osp.join(args.show_dir, name + ".disp.pred.npz"), "disp", (1, len(lefts), h, w),
                              np.uint16 if args.output == "disp_u16" else np.float32)
+            if args.motion:
+                ch = ops.MOTION_CHANNELS[args.motion]
+                mot = _NpzStream(osp.join(args.show_dir, name + ".motion.pred.npz"), "motion", (1, len(lefts), h, w, ch),
+                                 np.float32)
         n = 0
         for res in live_results(s, iter_frames(lefts, rights)):
             n += 1
+            if args.motion:
+                res, field = res
+                if mot is not None:
+                    mot.write(np.full((h, w, ch), np.nan, np.float32) if field is None else field)
             if out is not None:
                 out.write(res)
-        if out is not None:
-            out.close()
+        for stream in (out, mot):
+            if stream is not None:
+                stream.close()
         print(f"{name}: {n} frames")
     for s in sessions.values():
         s.close()

@@ -10,6 +10,11 @@ and a result the caller may keep, around the FrameRunner's captured frame graph:
 Ingest and export run on the compute stream, outside the graph, right before and after the replay; both copies run on
 streams of their own, ordered against the compute stream with events, so the upload of frame t+1 and the download of
 frame t-1 overlap the compute of frame t.  Every buffer is allocated once, at the first frame.
+
+With ``motion=`` the session also hands out the dense SE3 motion field the network estimates on every steady-state
+frame, as per-pixel optical flow, flow + disparity change, or metric 3-D scene flow: ``codd_export_motion`` runs right
+after ``codd_export_depth``, reads the field where the frame graph left it, and keeps the previous frame's depth map the
+field refers to in a buffer of the session's own, which it rolls forward in the same launch.
 """
 from collections import deque
 
@@ -20,6 +25,7 @@ from . import _abi, ops, synth
 from .runtime import FrameRunner
 
 OUTPUTS = ("disp", "depth", "disp_u16")
+MOTIONS = ("flow2d", "flow_dd", "sceneflow")
 DEPTH = 2  # frames in flight: input, device and host output slots are double-buffered
 
 
@@ -71,12 +77,24 @@ class LiveSession:
     its arrays at once; every result is a fresh numpy array owned by the caller.  At most ``DEPTH`` (2) frames are in
     flight: a further ``push`` first waits for the OLDEST frame's download and parks its result in an internal queue,
     which ``pop`` drains first -- results always come out in push order and no slot in flight is overwritten.
+
+    ``motion`` (None, "flow2d", "flow_dd" or "sceneflow"): with a mode set, ``pop`` and ``step`` return ``(result,
+    motion)``; ``motion`` is a caller-owned fp32 numpy [h,w,C] or None for a frame without a field (the first frame of a
+    sequence).  The vectors live on the PREVIOUS frame's pixel grid and point to the current frame (the convention of
+    RAFT-3D and of the scene-flow benchmarks): "flow2d" (C=2) optical flow in pixels; "flow_dd" (C=3) the same plus the
+    change of disparity in pixels; "sceneflow" (C=3) the 3-D displacement (X, Y, Z) in the unit of ``calib`` = fx *
+    baseline (metres for a metric baseline).  Pixels whose point is not in front of the camera before and after the
+    motion (depth below 0.05 normalised units) are NaN in every channel.
     """
 
     def __init__(self, estimator, shape, intrinsics=(1050.0, 1050.0, 480.0, 270.0), calib=210.0, output="depth",
-                 bgr=False, rectify=None, use_graph=True, divisor=64):
+                 bgr=False, rectify=None, use_graph=True, divisor=64, motion=None):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
+        if motion is not None and motion not in MOTIONS:
+            raise ValueError(f"motion: None or one of {MOTIONS} expected, got {motion!r}")
+        if motion is not None and getattr(estimator, "motion", None) is None:
+            raise ValueError(f"motion={motion!r} needs an estimator with a motion stage (this one has none)")
         h, w = int(shape[0]), int(shape[1])
         if h <= 0 or w <= 0:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
@@ -86,6 +104,11 @@ class LiveSession:
         # one sample's img_metas (the list the estimator's inference() is handed): [dict]
         self.metas = synth.default_metas(*self.padded, img_shape=(h, w, 3), intrinsics=tuple(intrinsics))[0]
         self.metas[0]["calib"] = self.calib
+        self.motion = motion
+        if motion is not None:
+            from .motion import Motion
+            self._K = [float(np.float32(v)) for v in self.metas[0]["intrinsics"]]  # as Motion.forward passes them
+            self._bf = Motion._bf(self.metas)
         self.runner = FrameRunner(estimator, self.metas, use_graph=use_graph)
         self._open_done = False
         self._pushed = 0
@@ -112,6 +135,12 @@ class LiveSession:
                                    for p in self._maps_host)
             self._d_out = torch.empty(h, w, dtype=odt, device=dev)
             self._h_out = [torch.empty(h, w, dtype=odt, pin_memory=True) for _ in range(DEPTH)]
+            if self.motion is not None:
+                ch = ops.MOTION_CHANNELS[self.motion]
+                self._depth_prev = torch.zeros(H, W, dtype=torch.float32, device=dev)  # (rolled before it is ever read)
+                self._d_mot = torch.empty(h, w, ch, dtype=torch.float32, device=dev)
+                self._h_mot = [torch.empty(h, w, ch, dtype=torch.float32, pin_memory=True) for _ in range(DEPTH)]
+                self._has_mot = [False] * DEPTH
             self._s_up, self._s_down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             ev = lambda: [torch.cuda.Event() for _ in range(DEPTH)]  # noqa: E731
             self._e_up, self._e_ingest, self._e_export, self._e_down = ev(), ev(), ev(), ev()
@@ -153,10 +182,17 @@ class LiveSession:
             if self._pushed > 0:
                 compute.wait_event(self._e_down[(self._pushed - 1) % DEPTH])  # one device staging buffer
             ops.export_depth(disp, self._d_out, mode=self.output, calib=self.calib)
+            if self.motion is not None:
+                Ts = self.runner.last.get("Ts")  # None: the frame has no field (first of a sequence) -- roll only
+                ops.export_motion(Ts, disp, self._depth_prev, self._d_mot, self.motion, self._K, self._bf,
+                                  scale=self.calib / self._bf)
+                self._has_mot[k] = Ts is not None
             self._e_export[k].record(compute)
             with torch.cuda.stream(self._s_down):
                 self._s_down.wait_event(self._e_export[k])
                 self._h_out[k].copy_(self._d_out, non_blocking=True)
+                if self.motion is not None and self._has_mot[k]:
+                    self._h_mot[k].copy_(self._d_mot, non_blocking=True)
                 self._e_down[k].record(self._s_down)
         self._inflight.append(k)
         self._pushed += 1
@@ -165,10 +201,14 @@ class LiveSession:
         k = self._inflight.popleft()
         self._e_down[k].synchronize()  # this frame's download only
         res = self._h_out[k].numpy().copy()
-        return res.view(np.uint16) if self.output == "disp_u16" else res
+        res = res.view(np.uint16) if self.output == "disp_u16" else res
+        if self.motion is None:
+            return res
+        return res, (self._h_mot[k].numpy().copy() if self._has_mot[k] else None)
 
     def pop(self):
-        """The oldest frame's result: numpy [h,w] (fp32, or uint16 for ``disp_u16``), owned by the caller."""
+        """The oldest frame's result: numpy [h,w] (fp32, or uint16 for ``disp_u16``), owned by the caller; with a
+        ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None."""
         if self._ready:
             return self._ready.popleft()
         if not self._inflight:
@@ -197,7 +237,7 @@ class LiveSession:
             self._s_up.synchronize()
             torch.cuda.current_stream(self.dev).synchronize()
             self._s_down.synchronize()
-            for name in ("_h_in", "_d_in", "_scratch", "_maps", "_d_out", "_h_out"):
+            for name in ("_h_in", "_d_in", "_scratch", "_maps", "_d_out", "_h_out", "_depth_prev", "_d_mot", "_h_mot"):
                 setattr(self, name, None)
             self._open_done = False
         self._inflight.clear()

@@ -1765,6 +1765,31 @@ def export_depth(disp, out, mode="disp", calib=1.0):
     return out
 
 
+MOTION_MODES = dict(flow2d=0, flow_dd=1, sceneflow=2)  # CODD_MOTION_* of include/codd_hip.h
+MOTION_CHANNELS = dict(flow2d=2, flow_dd=3, sceneflow=3)
+
+
+def export_motion(T, disp_cur, depth_prev, out, mode, K, bf, scale=1.0):
+    """One launch per frame: the up-sampled SE3 field ``T`` [1,H,W,7] (or None: the frame has no field) and the
+    previous frame's depth ``depth_prev`` [H,W] -> per-pixel motion of the cropped image in ``out`` [h,w,C] (fp32,
+    caller-owned; untouched when T is None), on the previous frame's grid, NaN where a point is not in front of the
+    camera; then depth_prev[:h,:w] becomes ``disp_to_depth(disp_cur, bf)[:h,:w]`` for the next frame.  ``mode``:
+    'flow2d' (C=2, pixels), 'flow_dd' (C=3, flow + disparity change in pixels), 'sceneflow' (C=3, scale * (X1 - X0))."""
+    lib = _abi.load()
+    _require_gpu(disp_cur)
+    H, W = disp_cur.shape[-2:]
+    h, w, ch = out.shape
+    assert ch == MOTION_CHANNELS[mode] and out.dtype == torch.float32 and out.is_cuda and out.is_contiguous()
+    for t in (disp_cur, depth_prev):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == H * W
+    if T is not None:
+        assert T.dtype == torch.float32 and T.is_cuda and T.is_contiguous() and T.numel() == H * W * 7 and T.shape[-1] == 7
+    _abi.check(lib.codd_export_motion(None if T is None else T.data_ptr(), disp_cur.data_ptr(), depth_prev.data_ptr(),
+                                      H, W, h, w, MOTION_MODES[mode], *[float(v) for v in K], float(bf), float(scale),
+                                      out.data_ptr(), _stream()), "export_motion")
+    return out
+
+
 def fusion_select(mode, cur, warp, gt=None, K=0.5):
     """mode 'kalman' / 'gt' (ablation fusions).  cur, warp [B,1,H,W]; gt [B,1,hg,wg]."""
     lib = _abi.load()

@@ -526,6 +526,32 @@ int codd_ingest_pair(const unsigned char* left, const unsigned char* right, int 
 #define CODD_EXPORT_DISP_U16 2
 int codd_export_depth(const float* disp, int H, int W, int h, int w, int mode, float calib, void* out, void* stream);
 
+/* Live-session motion export: the frame's up-sampled SE3 field T [H,W,7] (outputs["Ts"], batch 1; raft3d.py:268-270)
+ * -> per-pixel motion of the cropped h x w image, contiguous fp32 [h,w,C], in a caller-owned device staging buffer;
+ * and, in the same launch, the roll of the session's previous-frame depth map.  With X0 = inv_project(depth_prev, x, y,
+ * K), X1 = T * X0, a = project(X1), c = project(X0) (projective_ops.py:55-68 induced_flow; PEPS and MIN_DEPTH as there),
+ * mode:
+ *   CODD_MOTION_FLOW2D     C = 2: (a.x - c.x, a.y - c.y), optical flow in pixels;
+ *   CODD_MOTION_FLOW_DD    C = 3: the two above and bf * (a.z - c.z), the disparity change in pixels (the `est.z * bf`
+ *                          of the scene-flow metrics, model/codd.py:519-575);
+ *   CODD_MOTION_SCENEFLOW  C = 3: scale * (X1 - X0), the 3-D displacement; depth is in RAFT3D's normalised units
+ *                          (bf / disp), so scale = calib / bf gives the unit of calib = fx * baseline.
+ * The vectors live on the PREVIOUS frame's pixel grid and point to the current frame.  A pixel is valid iff
+ * X0.z >= MIN_DEPTH && X1.z >= MIN_DEPTH (false for NaN); an invalid pixel gets NaN in every channel.
+ * Roll: after reading depth_prev[y,x] ([H,W], read inside the crop only) the same lane overwrites it with
+ * clip(bf / (disp_cur[y,x] + 1e-5), 0, 210), the bits of codd_disp_to_depth (motion.py:154-165): the next frame finds this
+ * frame's depth there.  Elements outside the crop are neither read nor written.
+ * T == NULL: the frame has no field (first frame of a sequence): only the roll runs and out may be NULL.
+ * K = (fx, fy, cx, cy) at full resolution.  No pointer needs more than float alignment: spans that do not start or end
+ * on a 16-byte boundary take scalar heads and tails and give the same bits.
+ * CODD_EINVAL: disp_cur or depth_prev NULL; T without out; h > H or w > W; a non-positive size; an unknown mode; bf not
+ * > 0. */
+#define CODD_MOTION_FLOW2D 0
+#define CODD_MOTION_FLOW_DD 1
+#define CODD_MOTION_SCENEFLOW 2
+int codd_export_motion(const float* T, const float* disp_cur, float* depth_prev, int H, int W, int h, int w, int mode,
+                       float fx, float fy, float cx, float cy, float bf, float scale, float* out, void* stream);
+
 /* Ablation plug-ins.  codd_fusion_select: mode 0 = KalmanFusion (model/fusion/others.py:124-153; constant
  * gain K = Q/(Q+R), the reference never updates P), mode 1 = GTFusion (:54-86; gt [B,1,hg,wg], zero-padded).
  * cur, warp, out: [B,1,H,W]. */
