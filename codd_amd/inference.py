@@ -43,10 +43,17 @@ def parse_args(argv=None):
                    help="--live: also write <name>.motion.pred.npz, key motion, [1, frames, h, w, C] fp32: the per-pixel motion "
                    "from the previous frame to this one on the previous frame's grid (flow2d: pixels; flow_dd: + disparity "
                    "change; sceneflow: 3-D, in the unit of calib); NaN where invalid and in frames without a field")
+    p.add_argument("--ego", action="store_true",
+                   help="--live: also write <name>.ego.pred.npz: pose [1, frames, 7] (t in the unit of calib, q_xyzw: the rigid "
+                   "motion of static points from the previous camera frame to this one; its inverse is the camera's motion), "
+                   "stats [1, frames, 4] (ok, valid pixels, inliers, inlier rms in pixels), camera_to_world [1, frames, 4, 4] "
+                   "and moving [1, frames, h, w] uint8 (0 static, 1 moving, 255 invalid); a frame without a field is NaN / 255")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
     args = p.parse_args(argv)
     if args.motion is not None and not args.live:
         p.error("--motion needs --live")
+    if args.ego and not args.live:
+        p.error("--ego needs --live")
     return args
 
 
@@ -128,15 +135,20 @@ class _NpzStream:
     def write(self, a):
         self.f.write(np.ascontiguousarray(a).tobytes())
 
-    def close(self):
+    def close(self, extra=None):
+        """``extra``: {key: array} of further (small) members written whole."""
         self.f.close()
+        for key, a in (extra or {}).items():
+            with self.zip.open(key + ".npy", "w") as f:
+                np.lib.format.write_array(f, np.ascontiguousarray(a), allow_pickle=False)
         self.zip.close()
 
 
 def run_live(args, model, videos):
     """--live: one LiveSession per frame size, every video pushed through it frame by frame; with --show each video's
     results go to <show-dir>/<name>.disp.pred.npz ([1, frames, h, w], as the default path writes) and, with --motion,
-    <name>.motion.pred.npz ([1, frames, h, w, C]; a frame without a field is all NaN)."""
+    <name>.motion.pred.npz ([1, frames, h, w, C]; a frame without a field is all NaN) and, with --ego,
+    <name>.ego.pred.npz (pose, stats, camera_to_world, moving; a frame without a field is NaN, 255 in moving)."""
     from PIL import Image
     from .live import LiveSession
     maps = None
@@ -150,9 +162,12 @@ def run_live(args, model, videos):
         if s is None:
             s = sessions[(h, w)] = LiveSession(model, (h, w), intrinsics=CUSTOM["intrinsics"], calib=CUSTOM["calib"],
                                                output=args.output, bgr=False, rectify=maps, use_graph=not args.no_graph,
-                                               motion=args.motion)
+                                               motion=args.motion, **(dict(egomotion=True) if args.ego else {}))
         s.reset()
-        out = mot = None
+        out = mot = ego = None
+        nf = len(lefts)
+        pose, stats, world = (np.full((1, nf) + t, np.nan, dt) for t, dt in (((7,), np.float32), ((4,), np.float32),
+                                                                             ((4, 4), np.float64)))
         if args.show:
             os.makedirs(args.show_dir, exist_ok=True)
             out = _NpzStream(osp.join(args.show_dir, name + ".disp.pred.npz"), "disp", (1, len(lefts), h, w),
@@ -161,9 +176,18 @@ def run_live(args, model, videos):
                 ch = ops.MOTION_CHANNELS[args.motion]
                 mot = _NpzStream(osp.join(args.show_dir, name + ".motion.pred.npz"), "motion", (1, len(lefts), h, w, ch),
                                  np.float32)
+            if args.ego:
+                ego = _NpzStream(osp.join(args.show_dir, name + ".ego.pred.npz"), "moving", (1, nf, h, w), np.uint8)
         n = 0
         for res in live_results(s, iter_frames(lefts, rights)):
             n += 1
+            if args.ego:
+                res, e = res[:-1] if args.motion else res[0], res[-1]
+                if e is not None:
+                    pose[0, n - 1], world[0, n - 1] = e.pose, e.camera_to_world
+                    stats[0, n - 1] = (e.ok, e.valid, e.inliers, e.rms_px)
+                if ego is not None:
+                    ego.write(np.full((h, w), 255, np.uint8) if e is None else e.moving)
             if args.motion:
                 res, field = res
                 if mot is not None:
@@ -173,6 +197,8 @@ def run_live(args, model, videos):
         for stream in (out, mot):
             if stream is not None:
                 stream.close()
+        if ego is not None:
+            ego.close(dict(pose=pose, stats=stats, camera_to_world=world))
         print(f"{name}: {n} frames")
     for s in sessions.values():
         s.close()

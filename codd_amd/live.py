@@ -15,8 +15,13 @@ With ``motion=`` the session also hands out the dense SE3 motion field the netwo
 frame, as per-pixel optical flow, flow + disparity change, or metric 3-D scene flow: ``codd_export_motion`` runs right
 after ``codd_export_depth``, reads the field where the frame graph left it, and keeps the previous frame's depth map the
 field refers to in a buffer of the session's own, which it rolls forward in the same launch.
+
+With ``egomotion=`` the session separates that field into the camera's own motion and the pixels that moved on their
+own: ``codd_ego_motion`` runs between the two exports (it reads the previous depth map before ``codd_export_motion``
+rolls it), fits one rigid motion to the field robustly and marks the pixels whose flow disagrees with it; the camera
+trajectory is composed on the host when a result is collected.
 """
-from collections import deque
+from collections import deque, namedtuple
 
 import numpy as np
 import torch
@@ -27,6 +32,62 @@ from .runtime import FrameRunner
 OUTPUTS = ("disp", "depth", "disp_u16")
 MOTIONS = ("flow2d", "flow_dd", "sceneflow")
 DEPTH = 2  # frames in flight: input, device and host output slots are double-buffered
+EGO_DEFAULTS = dict(iters=5, delta_px=1.0, tau_px=2.0, min_valid=16)
+
+# One frame's ego-motion, caller-owned: pose fp32 [7] = (t, q_xyzw) of G, the rigid motion that maps static points from
+# the previous camera frame to the current one (t in the unit of calib; the camera itself moved by G^-1); ok (False: the
+# fit was degenerate and pose is its last good iterate); valid / inliers pixel counts; rms_px of the inliers; moving
+# uint8 [h,w] (0 static, 1 moving, 255 invalid) and residual fp32 [h,w] (pixels, NaN where invalid) on the previous
+# frame's grid; camera_to_world float64 [4,4], the current camera's pose in the frame of the sequence's first field.
+Ego = namedtuple("Ego", "pose ok valid inliers rms_px moving residual camera_to_world")
+
+
+def pose_matrix(pose):
+    """[t(3), q_xyzw(4)] -> the 4x4 float64 matrix of the rigid motion."""
+    t, (x, y, z, w) = np.asarray(pose[:3], np.float64), np.asarray(pose[3:7], np.float64)
+    n = x * x + y * y + z * z + w * w
+    s = 2.0 / n
+    M = np.eye(4)
+    M[:3, :3] = [[1 - s * (y * y + z * z), s * (x * y - z * w), s * (x * z + y * w)],
+                 [s * (x * y + z * w), 1 - s * (x * x + z * z), s * (y * z - x * w)],
+                 [s * (x * z - y * w), s * (y * z + x * w), 1 - s * (x * x + y * y)]]
+    M[:3, 3] = t
+    return M
+
+
+def trajectory_step(world, pose, ok=True):
+    """camera_to_world after one more frame: W_t = W_{t-1} G_t^-1.  ``pose`` None (a frame without a field) restarts
+    the trajectory at identity; ``ok`` False (a degenerate fit) carries ``world`` forward unchanged."""
+    if pose is None:
+        return np.eye(4)
+    if not ok:
+        return np.array(world, np.float64)
+    G = pose_matrix(pose)
+    Ginv = np.eye(4)
+    Ginv[:3, :3] = G[:3, :3].T
+    Ginv[:3, 3] = -G[:3, :3].T @ G[:3, 3]
+    return np.asarray(world, np.float64) @ Ginv
+
+
+def _check_ego(egomotion):
+    """False / None -> None; True -> the defaults; a dict overrides them.  ValueError otherwise (no device call)."""
+    if egomotion is None or egomotion is False:
+        return None
+    if egomotion is True:
+        return dict(EGO_DEFAULTS)
+    if not isinstance(egomotion, dict):
+        raise ValueError(f"egomotion: False, True or a dict of {tuple(EGO_DEFAULTS)} expected, got {egomotion!r}")
+    unknown = set(egomotion) - set(EGO_DEFAULTS)
+    if unknown:
+        raise ValueError(f"egomotion: unknown keys {sorted(unknown)}; known: {tuple(EGO_DEFAULTS)}")
+    p = dict(EGO_DEFAULTS, **egomotion)
+    if not (isinstance(p["iters"], int) and 1 <= p["iters"] <= 32):
+        raise ValueError(f"egomotion: iters in [1, 32] expected, got {p['iters']!r}")
+    for k in ("delta_px", "tau_px"):
+        if not float(p[k]) > 0:
+            raise ValueError(f"egomotion: positive {k} expected, got {p[k]!r}")
+    p["min_valid"] = int(p["min_valid"])
+    return p
 
 
 def check_frame(a, shape, name="frame"):
@@ -85,16 +146,23 @@ class LiveSession:
     change of disparity in pixels; "sceneflow" (C=3) the 3-D displacement (X, Y, Z) in the unit of ``calib`` = fx *
     baseline (metres for a metric baseline).  Pixels whose point is not in front of the camera before and after the
     motion (depth below 0.05 normalised units) are NaN in every channel.
+
+    ``egomotion`` (False, True, or a dict overriding ``iters``, ``delta_px``, ``tau_px``, ``min_valid``): ``pop`` and
+    ``step`` also return an ``Ego`` (or None for a frame without a field).  The tuple order is fixed:
+    ``result[, motion][, ego]``, each part present iff requested.
     """
 
     def __init__(self, estimator, shape, intrinsics=(1050.0, 1050.0, 480.0, 270.0), calib=210.0, output="depth",
-                 bgr=False, rectify=None, use_graph=True, divisor=64, motion=None):
+                 bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
             raise ValueError(f"motion: None or one of {MOTIONS} expected, got {motion!r}")
         if motion is not None and getattr(estimator, "motion", None) is None:
             raise ValueError(f"motion={motion!r} needs an estimator with a motion stage (this one has none)")
+        self.ego = _check_ego(egomotion)
+        if self.ego is not None and getattr(estimator, "motion", None) is None:
+            raise ValueError(f"egomotion={egomotion!r} needs an estimator with a motion stage (this one has none)")
         h, w = int(shape[0]), int(shape[1])
         if h <= 0 or w <= 0:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
@@ -105,7 +173,8 @@ class LiveSession:
         self.metas = synth.default_metas(*self.padded, img_shape=(h, w, 3), intrinsics=tuple(intrinsics))[0]
         self.metas[0]["calib"] = self.calib
         self.motion = motion
-        if motion is not None:
+        self._world = np.eye(4)  # camera_to_world of the last collected frame
+        if motion is not None or self.ego is not None:
             from .motion import Motion
             self._K = [float(np.float32(v)) for v in self.metas[0]["intrinsics"]]  # as Motion.forward passes them
             self._bf = Motion._bf(self.metas)
@@ -135,9 +204,19 @@ class LiveSession:
                                    for p in self._maps_host)
             self._d_out = torch.empty(h, w, dtype=odt, device=dev)
             self._h_out = [torch.empty(h, w, dtype=odt, pin_memory=True) for _ in range(DEPTH)]
+            if self.motion is not None or self.ego is not None:
+                self._depth_prev = torch.zeros(H, W, dtype=torch.float32, device=dev)  # (rolled before it is ever read)
+            if self.ego is not None:
+                self._d_ego = (torch.zeros(16, dtype=torch.float32, device=dev),
+                               torch.empty(h, w, dtype=torch.uint8, device=dev),
+                               torch.empty(h, w, dtype=torch.float32, device=dev))
+                self._h_ego = [(torch.empty(16, dtype=torch.float32, pin_memory=True),
+                                torch.empty(h, w, dtype=torch.uint8, pin_memory=True),
+                                torch.empty(h, w, dtype=torch.float32, pin_memory=True)) for _ in range(DEPTH)]
+                self._ego_scratch = torch.empty(ops.ego_motion_scratch(h, w), dtype=torch.uint8, device=dev)
+                self._has_ego = [False] * DEPTH
             if self.motion is not None:
                 ch = ops.MOTION_CHANNELS[self.motion]
-                self._depth_prev = torch.zeros(H, W, dtype=torch.float32, device=dev)  # (rolled before it is ever read)
                 self._d_mot = torch.empty(h, w, ch, dtype=torch.float32, device=dev)
                 self._h_mot = [torch.empty(h, w, ch, dtype=torch.float32, pin_memory=True) for _ in range(DEPTH)]
                 self._has_mot = [False] * DEPTH
@@ -182,17 +261,30 @@ class LiveSession:
             if self._pushed > 0:
                 compute.wait_event(self._e_down[(self._pushed - 1) % DEPTH])  # one device staging buffer
             ops.export_depth(disp, self._d_out, mode=self.output, calib=self.calib)
-            if self.motion is not None:
+            Ts = None
+            if self.motion is not None or self.ego is not None:
                 Ts = self.runner.last.get("Ts")  # None: the frame has no field (first of a sequence) -- roll only
+            if self.ego is not None:
+                if Ts is not None:  # (before export_motion rolls the depth map the field refers to)
+                    rec, mov, res = self._d_ego
+                    ops.ego_motion(Ts, self._depth_prev, self._K, self.shape, rec, mov, res, scale=self.calib / self._bf,
+                                   scratch=self._ego_scratch, **self.ego)
+                self._has_ego[k] = Ts is not None
+            if self.motion is not None:
                 ops.export_motion(Ts, disp, self._depth_prev, self._d_mot, self.motion, self._K, self._bf,
                                   scale=self.calib / self._bf)
                 self._has_mot[k] = Ts is not None
+            elif self.ego is not None:
+                ops.export_motion(None, disp, self._depth_prev, None, "sceneflow", self._K, self._bf, crop=self.shape)
             self._e_export[k].record(compute)
             with torch.cuda.stream(self._s_down):
                 self._s_down.wait_event(self._e_export[k])
                 self._h_out[k].copy_(self._d_out, non_blocking=True)
                 if self.motion is not None and self._has_mot[k]:
                     self._h_mot[k].copy_(self._d_mot, non_blocking=True)
+                if self.ego is not None and self._has_ego[k]:
+                    for host, dev_buf in zip(self._h_ego[k], self._d_ego):
+                        host.copy_(dev_buf, non_blocking=True)
                 self._e_down[k].record(self._s_down)
         self._inflight.append(k)
         self._pushed += 1
@@ -202,13 +294,26 @@ class LiveSession:
         self._e_down[k].synchronize()  # this frame's download only
         res = self._h_out[k].numpy().copy()
         res = res.view(np.uint16) if self.output == "disp_u16" else res
-        if self.motion is None:
-            return res
-        return res, (self._h_mot[k].numpy().copy() if self._has_mot[k] else None)
+        out = [res]
+        if self.motion is not None:
+            out.append(self._h_mot[k].numpy().copy() if self._has_mot[k] else None)
+        if self.ego is not None:
+            out.append(self._collect_ego(k))
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def _collect_ego(self, k):
+        if not self._has_ego[k]:
+            self._world = trajectory_step(self._world, None)
+            return None
+        rec, moving, residual = (t.numpy().copy() for t in self._h_ego[k])
+        pose, ok = rec[:7].copy(), bool(rec[7] != 0)
+        self._world = trajectory_step(self._world, pose, ok)
+        return Ego(pose, ok, int(rec[8]), int(rec[9]), float(rec[10]), moving, residual, self._world.copy())
 
     def pop(self):
         """The oldest frame's result: numpy [h,w] (fp32, or uint16 for ``disp_u16``), owned by the caller; with a
-        ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None."""
+        ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None; with ``egomotion``, an ``Ego`` or None comes
+        last."""
         if self._ready:
             return self._ready.popleft()
         if not self._inflight:
@@ -237,7 +342,8 @@ class LiveSession:
             self._s_up.synchronize()
             torch.cuda.current_stream(self.dev).synchronize()
             self._s_down.synchronize()
-            for name in ("_h_in", "_d_in", "_scratch", "_maps", "_d_out", "_h_out", "_depth_prev", "_d_mot", "_h_mot"):
+            for name in ("_h_in", "_d_in", "_scratch", "_maps", "_d_out", "_h_out", "_depth_prev", "_d_mot", "_h_mot",
+                         "_d_ego", "_h_ego", "_ego_scratch"):
                 setattr(self, name, None)
             self._open_done = False
         self._inflight.clear()

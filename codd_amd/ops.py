@@ -1769,25 +1769,66 @@ MOTION_MODES = dict(flow2d=0, flow_dd=1, sceneflow=2)  # CODD_MOTION_* of includ
 MOTION_CHANNELS = dict(flow2d=2, flow_dd=3, sceneflow=3)
 
 
-def export_motion(T, disp_cur, depth_prev, out, mode, K, bf, scale=1.0):
+def export_motion(T, disp_cur, depth_prev, out, mode, K, bf, scale=1.0, crop=None):
     """One launch per frame: the up-sampled SE3 field ``T`` [1,H,W,7] (or None: the frame has no field) and the
     previous frame's depth ``depth_prev`` [H,W] -> per-pixel motion of the cropped image in ``out`` [h,w,C] (fp32,
     caller-owned; untouched when T is None), on the previous frame's grid, NaN where a point is not in front of the
     camera; then depth_prev[:h,:w] becomes ``disp_to_depth(disp_cur, bf)[:h,:w]`` for the next frame.  ``mode``:
-    'flow2d' (C=2, pixels), 'flow_dd' (C=3, flow + disparity change in pixels), 'sceneflow' (C=3, scale * (X1 - X0))."""
+    'flow2d' (C=2, pixels), 'flow_dd' (C=3, flow + disparity change in pixels), 'sceneflow' (C=3, scale * (X1 - X0)).
+    ``out`` may be None when T is None (only the roll runs); ``crop`` = (h, w) then says which part is rolled."""
     lib = _abi.load()
     _require_gpu(disp_cur)
     H, W = disp_cur.shape[-2:]
-    h, w, ch = out.shape
-    assert ch == MOTION_CHANNELS[mode] and out.dtype == torch.float32 and out.is_cuda and out.is_contiguous()
+    if out is None:
+        assert T is None and crop is not None
+        h, w = int(crop[0]), int(crop[1])
+    else:
+        h, w, ch = out.shape
+        assert ch == MOTION_CHANNELS[mode] and out.dtype == torch.float32 and out.is_cuda and out.is_contiguous()
     for t in (disp_cur, depth_prev):
         assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == H * W
     if T is not None:
         assert T.dtype == torch.float32 and T.is_cuda and T.is_contiguous() and T.numel() == H * W * 7 and T.shape[-1] == 7
     _abi.check(lib.codd_export_motion(None if T is None else T.data_ptr(), disp_cur.data_ptr(), depth_prev.data_ptr(),
                                       H, W, h, w, MOTION_MODES[mode], *[float(v) for v in K], float(bf), float(scale),
-                                      out.data_ptr(), _stream()), "export_motion")
+                                      None if out is None else out.data_ptr(), _stream()), "export_motion")
     return out
+
+
+def ego_motion_scratch(h, w):
+    """Bytes of scratch ``ego_motion`` needs for an h x w crop (codd_ego_motion_scratch)."""
+    n = int(_abi.load().codd_ego_motion_scratch(int(h), int(w)))
+    if n <= 0:
+        raise ValueError(f"ego_motion_scratch: positive (h, w) expected, got {(h, w)}")
+    return n
+
+
+def ego_motion(T, depth_prev, K, crop, record, moving, residual=None, scale=1.0, iters=5, delta_px=1.0, tau_px=2.0,
+               min_valid=16, scratch=None):
+    """The camera's rigid motion between the previous and the current frame, fitted robustly to the SE3 field ``T``
+    [1,H,W,7] over the ``crop`` (h, w) of the previous frame's depth ``depth_prev`` [H,W] (read only), and the pixels
+    that moved on their own (include/codd_hip.h, codd_ego_motion).  Outputs are caller-owned device tensors: ``record``
+    fp32 [16] (scale * t, q_xyzw, ok, valid, inliers, rms_px, steps), ``moving`` uint8 [h,w] (0 static, 1 moving, 255
+    invalid), ``residual`` fp32 [h,w] or None.  ``scratch``: a uint8 tensor of ``ego_motion_scratch(h, w)`` bytes;
+    allocated here when None.  iters + 1 launches on the current stream, no host synchronisation."""
+    lib = _abi.load()
+    _require_gpu(T)
+    H, W = depth_prev.shape[-2:]
+    h, w = int(crop[0]), int(crop[1])
+    assert T.dtype == torch.float32 and T.is_cuda and T.is_contiguous() and T.numel() == H * W * 7 and T.shape[-1] == 7
+    assert depth_prev.dtype == torch.float32 and depth_prev.is_cuda and depth_prev.is_contiguous() and depth_prev.numel() == H * W
+    assert record.dtype == torch.float32 and record.is_cuda and record.is_contiguous() and record.numel() == 16
+    assert moving.dtype == torch.uint8 and moving.is_cuda and moving.is_contiguous() and tuple(moving.shape) == (h, w)
+    if residual is not None:
+        assert residual.dtype == torch.float32 and residual.is_cuda and residual.is_contiguous() and tuple(residual.shape) == (h, w)
+    if scratch is None:
+        scratch = torch.empty(ego_motion_scratch(h, w), dtype=torch.uint8, device=T.device)
+    assert scratch.dtype == torch.uint8 and scratch.is_cuda and scratch.is_contiguous()
+    _abi.check(lib.codd_ego_motion(T.data_ptr(), depth_prev.data_ptr(), H, W, h, w, *[float(v) for v in K], float(scale),
+                                   int(iters), float(delta_px), float(tau_px), int(min_valid), scratch.data_ptr(),
+                                   scratch.numel(), record.data_ptr(), moving.data_ptr(),
+                                   None if residual is None else residual.data_ptr(), _stream()), "ego_motion")
+    return record
 
 
 def fusion_select(mode, cur, warp, gt=None, K=0.5):

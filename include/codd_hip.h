@@ -552,6 +552,34 @@ int codd_export_depth(const float* disp, int H, int W, int h, int w, int mode, f
 int codd_export_motion(const float* T, const float* disp_cur, float* depth_prev, int H, int W, int h, int w, int mode,
                        float fx, float fy, float cx, float cy, float bf, float scale, float* out, void* stream);
 
+/* Live-session ego-motion: the camera's rigid motion G between the previous and the current frame, fitted to the
+ * frame's up-sampled SE3 field T [H,W,7] (outputs["Ts"], batch 1; raft3d.py:268-270) over the cropped h x w image, and
+ * the pixels that moved on their own.  The reference has no such output; this replaces the robust rigid fit a user of
+ * that field writes with torch (dozens of launches over every pixel and a host sync for the 6x6 solve per iteration).
+ * Per crop pixel X0 = inv_project(depth_prev, x, y, K), X1 = T * X0 (projective_ops.py:25-41, :55-68; PEPS and MIN_DEPTH
+ * as there); it is valid iff X0.z >= MIN_DEPTH && X1.z >= MIN_DEPTH and all six coordinates are finite.
+ * G maps static points from the previous camera frame to the current one (G^-1 is the camera's own motion).  It is found
+ * by `iters` Gauss-Newton / IRLS steps from identity over the valid pixels: Y = G_k X0, r = Y - X1, e^2 = |r|^2 / Z0^2,
+ * delta = delta_px / fx; weight 1 / Z0^2 in step 0 and 1 / (Z0^2 (1 + e^2 / delta^2)) (Cauchy) afterwards;
+ * H = sum w J^T J, g = sum w J^T r with J = [I | -[Y]x] in se3_exp's (tau, phi) order; xi = -H^-1 g by Cholesky;
+ * G_{k+1} = se3_exp(xi) * G_k, quaternion renormalised, rounded to fp32.  Per-pixel terms are fp32, sums and the solve
+ * fp64, every sum in a fixed order: equal inputs give equal bits.  The fit stops with ok = 0 at the last good iterate
+ * (identity if none) when fewer than min_valid pixels are valid, a Cholesky pivot (the diagonal entry before its square
+ * root) is <= 1e-12 * trace(H), or a sum is not finite.
+ * Outputs, all caller-owned: record, 16 fp32: [0:3] scale * t, [3:7] q_xyzw, [7] ok, [8] valid pixels, [9] inliers
+ * (e <= delta under the final G), [10] sqrt(mean e^2 over the inliers) * fx (pixels; 0 without inliers), [11] steps taken,
+ * [12:16] zero -- never NaN; moving [h,w] bytes: 0 static, 1 where the residual flow |project(X1).xy - project(G X0).xy|
+ * exceeds tau_px, 255 invalid; residual [h,w] fp32 (may be NULL): that magnitude in pixels, NaN where invalid.
+ * depth_prev [H,W] is read inside the crop only and not written (codd_export_motion rolls it; call this first).
+ * scratch: codd_ego_motion_scratch(h, w) bytes (-1 for a non-positive size), contents irrelevant, any alignment.
+ * No pointer needs more than float alignment (moving: none).  iters + 1 launches, no host synchronisation.
+ * CODD_EINVAL, before any launch: T, depth_prev, scratch, record or moving NULL; a non-positive size, h > H or w > W;
+ * iters outside [1, 32]; fx, fy, delta_px or tau_px not > 0; scratch_bytes below the size function's answer. */
+long long codd_ego_motion_scratch(int h, int w);
+int codd_ego_motion(const float* T, const float* depth_prev, int H, int W, int h, int w, float fx, float fy, float cx,
+                    float cy, float scale, int iters, float delta_px, float tau_px, int min_valid, void* scratch,
+                    long long scratch_bytes, float* record, unsigned char* moving, float* residual, void* stream);
+
 /* Ablation plug-ins.  codd_fusion_select: mode 0 = KalmanFusion (model/fusion/others.py:124-153; constant
  * gain K = Q/(Q+R), the reference never updates P), mode 1 = GTFusion (:54-86; gt [B,1,hg,wg], zero-padded).
  * cur, warp, out: [B,1,H,W]. */
