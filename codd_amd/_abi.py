@@ -124,6 +124,7 @@ SIGNATURES = {
     "codd_export_motion": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p]),
     "codd_ego_motion_scratch": (_ll, [_i, _i]),
     "codd_ego_motion": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _i, _p, _ll, _p, _p, _p, _p]),
+    "codd_export_confidence": (_i, [_p, _p, _p, _i, _i, _i, _i, c_float_p, _f, _f, _p, _p, _p]),
 }
 
 ABI_VERSION = 12  # CODD_ABI_VERSION of include/codd_hip.h

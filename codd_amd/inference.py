@@ -48,12 +48,22 @@ def parse_args(argv=None):
                    "motion of static points from the previous camera frame to this one; its inverse is the camera's motion), "
                    "stats [1, frames, 4] (ok, valid pixels, inliers, inlier rms in pixels), camera_to_world [1, frames, 4, 4] "
                    "and moving [1, frames, h, w] uint8 (0 static, 1 moving, 255 invalid); a frame without a field is NaN / 255")
+    p.add_argument("--confidence", action="store_true",
+                   help="--live: also write <name>.conf.pred.npz: flags [1, frames, h, w] uint8 (the OR of 1 out of view, 2 "
+                   "occluded in the right image, 4 photometric mismatch; 128 invalid disparity; 0: a pixel to trust) and "
+                   "residual [1, frames, h, w] fp32 (grey levels; NaN where the flags are 1 or 128)")
+    p.add_argument("--occ-px", type=float, default=None, help="--confidence: occlusion tolerance in pixels (default 1.0)")
+    p.add_argument("--tau", type=float, default=None, help="--confidence: mismatch threshold in grey levels (default 24.0)")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
     args = p.parse_args(argv)
     if args.motion is not None and not args.live:
         p.error("--motion needs --live")
     if args.ego and not args.live:
         p.error("--ego needs --live")
+    if args.confidence and not args.live:
+        p.error("--confidence needs --live")
+    if (args.occ_px is not None or args.tau is not None) and not args.confidence:
+        p.error("--occ-px / --tau need --confidence")
     return args
 
 
@@ -127,6 +137,7 @@ class _NpzStream:
 
     def __init__(self, path, key, shape, dtype):
         import zipfile
+        self.spooled = None
         self.zip = zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, allowZip64=True)
         self.f = self.zip.open(key + ".npy", "w", force_zip64=True)
         np.lib.format.write_array_header_1_0(self.f, dict(descr=np.lib.format.dtype_to_descr(np.dtype(dtype)),
@@ -135,26 +146,70 @@ class _NpzStream:
     def write(self, a):
         self.f.write(np.ascontiguousarray(a).tobytes())
 
+    def spool(self, key, shape, dtype):
+        """A second member that grows alongside the first (a zip archive takes one member at a time): its frames go to an
+        anonymous temporary file next to the archive, which ``close`` copies into the archive in chunks; the file
+        vanishes with the process if ``close`` is never reached.  Returns the object to ``write`` frames to."""
+        import tempfile
+        tmp = tempfile.TemporaryFile(dir=osp.dirname(osp.abspath(self.zip.filename)))
+        self.spooled = (key, tuple(shape), np.dtype(dtype), tmp)
+        return _Spool(tmp, dtype)
+
     def close(self, extra=None):
         """``extra``: {key: array} of further (small) members written whole."""
         self.f.close()
+        if self.spooled:
+            key, shape, dtype, tmp = self.spooled
+            try:
+                tmp.seek(0)
+                with self.zip.open(key + ".npy", "w", force_zip64=True) as f:
+                    np.lib.format.write_array_header_1_0(f, dict(descr=np.lib.format.dtype_to_descr(dtype),
+                                                                 fortran_order=False, shape=shape))
+                    for chunk in iter(lambda: tmp.read(1 << 22), b""):
+                        f.write(chunk)
+            finally:
+                tmp.close()
         for key, a in (extra or {}).items():
             with self.zip.open(key + ".npy", "w") as f:
                 np.lib.format.write_array(f, np.ascontiguousarray(a), allow_pickle=False)
         self.zip.close()
+
+    def abort(self):
+        """Give up on a half-written archive: close what is open and remove the file, so that no truncated result is
+        left where a complete one is expected."""
+        try:
+            self.f.close()
+            if self.spooled:
+                self.spooled[3].close()
+            self.zip.close()
+        finally:
+            if osp.exists(self.zip.filename):
+                os.remove(self.zip.filename)
+
+
+class _Spool:
+    def __init__(self, f, dtype):
+        self.f, self.dtype = f, np.dtype(dtype)
+
+    def write(self, a):
+        self.f.write(np.ascontiguousarray(a, dtype=self.dtype).tobytes())
 
 
 def run_live(args, model, videos):
     """--live: one LiveSession per frame size, every video pushed through it frame by frame; with --show each video's
     results go to <show-dir>/<name>.disp.pred.npz ([1, frames, h, w], as the default path writes) and, with --motion,
     <name>.motion.pred.npz ([1, frames, h, w, C]; a frame without a field is all NaN) and, with --ego,
-    <name>.ego.pred.npz (pose, stats, camera_to_world, moving; a frame without a field is NaN, 255 in moving)."""
+    <name>.ego.pred.npz (pose, stats, camera_to_world, moving; a frame without a field is NaN, 255 in moving) and, with
+    --confidence, <name>.conf.pred.npz (flags and residual, [1, frames, h, w] each)."""
     from PIL import Image
     from .live import LiveSession
     maps = None
     if args.rectify_maps:
         z = np.load(args.rectify_maps)
         maps = ((z["left_x"], z["left_y"]), (z["right_x"], z["right_y"]))
+    extra = dict(egomotion=True) if args.ego else {}
+    if args.confidence:
+        extra["confidence"] = {k: v for k, v in (("occ_px", args.occ_px), ("tau", args.tau)) if v is not None} or True
     sessions = {}
     for name, lefts, rights in videos:
         w, h = Image.open(lefts[0]).size
@@ -162,9 +217,9 @@ def run_live(args, model, videos):
         if s is None:
             s = sessions[(h, w)] = LiveSession(model, (h, w), intrinsics=CUSTOM["intrinsics"], calib=CUSTOM["calib"],
                                                output=args.output, bgr=False, rectify=maps, use_graph=not args.no_graph,
-                                               motion=args.motion, **(dict(egomotion=True) if args.ego else {}))
+                                               motion=args.motion, **extra)
         s.reset()
-        out = mot = ego = None
+        out = mot = ego = cflags = cres = None
         nf = len(lefts)
         pose, stats, world = (np.full((1, nf) + t, np.nan, dt) for t, dt in (((7,), np.float32), ((4,), np.float32),
                                                                              ((4, 4), np.float64)))
@@ -178,27 +233,42 @@ def run_live(args, model, videos):
                                  np.float32)
             if args.ego:
                 ego = _NpzStream(osp.join(args.show_dir, name + ".ego.pred.npz"), "moving", (1, nf, h, w), np.uint8)
+            if args.confidence:
+                cflags = _NpzStream(osp.join(args.show_dir, name + ".conf.pred.npz"), "flags", (1, nf, h, w), np.uint8)
+                cres = cflags.spool("residual", (1, nf, h, w), np.float32)
         n = 0
-        for res in live_results(s, iter_frames(lefts, rights)):
-            n += 1
-            if args.ego:
-                res, e = res[:-1] if args.motion else res[0], res[-1]
-                if e is not None:
-                    pose[0, n - 1], world[0, n - 1] = e.pose, e.camera_to_world
-                    stats[0, n - 1] = (e.ok, e.valid, e.inliers, e.rms_px)
-                if ego is not None:
-                    ego.write(np.full((h, w), 255, np.uint8) if e is None else e.moving)
-            if args.motion:
-                res, field = res
-                if mot is not None:
-                    mot.write(np.full((h, w, ch), np.nan, np.float32) if field is None else field)
-            if out is not None:
-                out.write(res)
+        try:
+            for res in live_results(s, iter_frames(lefts, rights)):
+                n += 1
+                if args.confidence:
+                    res, c = res[:-1] if (args.motion or args.ego) else res[0], res[-1]
+                    if cflags is not None:
+                        cflags.write(c.flags)
+                        cres.write(c.residual)
+                if args.ego:
+                    res, e = res[:-1] if args.motion else res[0], res[-1]
+                    if e is not None:
+                        pose[0, n - 1], world[0, n - 1] = e.pose, e.camera_to_world
+                        stats[0, n - 1] = (e.ok, e.valid, e.inliers, e.rms_px)
+                    if ego is not None:
+                        ego.write(np.full((h, w), 255, np.uint8) if e is None else e.moving)
+                if args.motion:
+                    res, field = res
+                    if mot is not None:
+                        mot.write(np.full((h, w, ch), np.nan, np.float32) if field is None else field)
+                if out is not None:
+                    out.write(res)
+        except BaseException:  # (no truncated <name>.conf.pred.npz behind a failed run)
+            if cflags is not None:
+                cflags.abort()
+            raise
         for stream in (out, mot):
             if stream is not None:
                 stream.close()
         if ego is not None:
             ego.close(dict(pose=pose, stats=stats, camera_to_world=world))
+        if cflags is not None:
+            cflags.close()
         print(f"{name}: {n} frames")
     for s in sessions.values():
         s.close()

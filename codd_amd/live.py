@@ -20,6 +20,11 @@ With ``egomotion=`` the session separates that field into the camera's own motio
 own: ``codd_ego_motion`` runs between the two exports (it reads the previous depth map before ``codd_export_motion``
 rolls it), fits one rigid motion to the field robustly and marks the pixels whose flow disagrees with it; the camera
 trajectory is composed on the host when a result is collected.
+
+With ``confidence=`` the session says which depth pixels to trust: ``codd_export_confidence`` runs right after
+``codd_export_depth`` on the frame's disparity and on the two normalised images the frame graph read -- the buffers the
+``fill`` closure below was handed for this frame, which the graph only reads -- and returns per-pixel flags (out of view,
+occluded in the right image, photometric mismatch, invalid) and the photometric residual.  It needs no motion stage.
 """
 from collections import deque, namedtuple
 
@@ -33,6 +38,7 @@ OUTPUTS = ("disp", "depth", "disp_u16")
 MOTIONS = ("flow2d", "flow_dd", "sceneflow")
 DEPTH = 2  # frames in flight: input, device and host output slots are double-buffered
 EGO_DEFAULTS = dict(iters=5, delta_px=1.0, tau_px=2.0, min_valid=16)
+CONF_DEFAULTS = dict(occ_px=1.0, tau=24.0)
 
 # One frame's ego-motion, caller-owned: pose fp32 [7] = (t, q_xyzw) of G, the rigid motion that maps static points from
 # the previous camera frame to the current one (t in the unit of calib; the camera itself moved by G^-1); ok (False: the
@@ -40,6 +46,14 @@ EGO_DEFAULTS = dict(iters=5, delta_px=1.0, tau_px=2.0, min_valid=16)
 # uint8 [h,w] (0 static, 1 moving, 255 invalid) and residual fp32 [h,w] (pixels, NaN where invalid) on the previous
 # frame's grid; camera_to_world float64 [4,4], the current camera's pose in the frame of the sequence's first field.
 Ego = namedtuple("Ego", "pose ok valid inliers rms_px moving residual camera_to_world")
+
+
+# One frame's stereo confidence on the CURRENT frame's grid, caller-owned: flags uint8 [h,w], the OR of 1 (out of view: the
+# match falls left of the right image), 2 (occluded in the right image), 4 (photometric mismatch: residual > tau) and 128
+# (disparity not finite or not positive; alone) -- 0 is a pixel to trust; residual fp32 [h,w], the mean absolute
+# difference of the left pixel and its match in the right image in grey levels of the 8-bit source, NaN where the flags
+# are 1 or 128.
+Confidence = namedtuple("Confidence", "flags residual")
 
 
 def pose_matrix(pose):
@@ -87,6 +101,30 @@ def _check_ego(egomotion):
         if not float(p[k]) > 0:
             raise ValueError(f"egomotion: positive {k} expected, got {p[k]!r}")
     p["min_valid"] = int(p["min_valid"])
+    return p
+
+
+def _check_conf(confidence):
+    """False / None -> None; True -> the defaults; a dict overrides them.  ValueError otherwise (no device call)."""
+    if confidence is None or confidence is False:
+        return None
+    if confidence is True:
+        return dict(CONF_DEFAULTS)
+    if not isinstance(confidence, dict):
+        raise ValueError(f"confidence: False, True or a dict of {tuple(CONF_DEFAULTS)} expected, got {confidence!r}")
+    unknown = set(confidence) - set(CONF_DEFAULTS)
+    if unknown:
+        raise ValueError(f"confidence: unknown keys {sorted(unknown)}; known: {tuple(CONF_DEFAULTS)}")
+    p = {}
+    for k, v in dict(CONF_DEFAULTS, **confidence).items():
+        try:
+            p[k] = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"confidence: a number expected for {k}, got {v!r}") from None
+    if not p["occ_px"] >= 0:  # (NaN compares false)
+        raise ValueError(f"confidence: occ_px >= 0 expected, got {confidence['occ_px']!r}")
+    if p["tau"] != p["tau"]:
+        raise ValueError("confidence: tau must not be NaN")
     return p
 
 
@@ -149,11 +187,15 @@ class LiveSession:
 
     ``egomotion`` (False, True, or a dict overriding ``iters``, ``delta_px``, ``tau_px``, ``min_valid``): ``pop`` and
     ``step`` also return an ``Ego`` (or None for a frame without a field).  The tuple order is fixed:
-    ``result[, motion][, ego]``, each part present iff requested.
+    ``result[, motion][, ego][, confidence]``, each part present iff requested.
+
+    ``confidence`` (False, True, or a dict overriding ``occ_px`` (1.0 pixel) and ``tau`` (24.0 grey levels)): ``pop`` and
+    ``step`` also return a ``Confidence(flags, residual)`` on the CURRENT frame's grid, for every frame (never None).  It
+    needs no motion stage.
     """
 
     def __init__(self, estimator, shape, intrinsics=(1050.0, 1050.0, 480.0, 270.0), calib=210.0, output="depth",
-                 bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False):
+                 bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
@@ -163,6 +205,7 @@ class LiveSession:
         self.ego = _check_ego(egomotion)
         if self.ego is not None and getattr(estimator, "motion", None) is None:
             raise ValueError(f"egomotion={egomotion!r} needs an estimator with a motion stage (this one has none)")
+        self.conf = _check_conf(confidence)
         h, w = int(shape[0]), int(shape[1])
         if h <= 0 or w <= 0:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
@@ -220,6 +263,11 @@ class LiveSession:
                 self._d_mot = torch.empty(h, w, ch, dtype=torch.float32, device=dev)
                 self._h_mot = [torch.empty(h, w, ch, dtype=torch.float32, pin_memory=True) for _ in range(DEPTH)]
                 self._has_mot = [False] * DEPTH
+            if self.conf is not None:
+                self._d_conf = (torch.empty(h, w, dtype=torch.uint8, device=dev),
+                                torch.empty(h, w, dtype=torch.float32, device=dev))
+                self._h_conf = [(torch.empty(h, w, dtype=torch.uint8, pin_memory=True),
+                                 torch.empty(h, w, dtype=torch.float32, pin_memory=True)) for _ in range(DEPTH)]
             self._s_up, self._s_down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             ev = lambda: [torch.cuda.Event() for _ in range(DEPTH)]  # noqa: E731
             self._e_up, self._e_ingest, self._e_export, self._e_down = ev(), ev(), ev(), ev()
@@ -253,7 +301,10 @@ class LiveSession:
                 self._e_up[k].record(self._s_up)
             compute.wait_event(self._e_up[k])
 
+            images = []  # (emptied per frame: a fill that is skipped cannot leave the previous frame's buffers here)
+
             def fill(left, right):
+                images[:] = (left, right)  # (the frame's normalised images: read again by export_confidence)
                 ops.ingest_pair(self._d_in[k][0], self._d_in[k][1], left, right, bgr=self.bgr, maps=self._maps)
                 self._e_ingest[k].record(compute)
 
@@ -261,6 +312,10 @@ class LiveSession:
             if self._pushed > 0:
                 compute.wait_event(self._e_down[(self._pushed - 1) % DEPTH])  # one device staging buffer
             ops.export_depth(disp, self._d_out, mode=self.output, calib=self.calib)
+            if self.conf is not None:
+                # step_fill calls fill exactly once per frame, on every path: the buffers it was handed are this frame's
+                assert len(images) == 2, "FrameRunner.step_fill did not call fill(left, right)"
+                ops.export_confidence(disp, self._d_conf[0], self._d_conf[1], images[0], images[1], **self.conf)
             Ts = None
             if self.motion is not None or self.ego is not None:
                 Ts = self.runner.last.get("Ts")  # None: the frame has no field (first of a sequence) -- roll only
@@ -285,6 +340,9 @@ class LiveSession:
                 if self.ego is not None and self._has_ego[k]:
                     for host, dev_buf in zip(self._h_ego[k], self._d_ego):
                         host.copy_(dev_buf, non_blocking=True)
+                if self.conf is not None:
+                    for host, dev_buf in zip(self._h_conf[k], self._d_conf):
+                        host.copy_(dev_buf, non_blocking=True)
                 self._e_down[k].record(self._s_down)
         self._inflight.append(k)
         self._pushed += 1
@@ -299,6 +357,8 @@ class LiveSession:
             out.append(self._h_mot[k].numpy().copy() if self._has_mot[k] else None)
         if self.ego is not None:
             out.append(self._collect_ego(k))
+        if self.conf is not None:
+            out.append(Confidence(*(t.numpy().copy() for t in self._h_conf[k])))
         return out[0] if len(out) == 1 else tuple(out)
 
     def _collect_ego(self, k):
@@ -312,8 +372,8 @@ class LiveSession:
 
     def pop(self):
         """The oldest frame's result: numpy [h,w] (fp32, or uint16 for ``disp_u16``), owned by the caller; with a
-        ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None; with ``egomotion``, an ``Ego`` or None comes
-        last."""
+        ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None; with ``egomotion``, an ``Ego`` or None
+        follows; with ``confidence``, a ``Confidence`` comes last."""
         if self._ready:
             return self._ready.popleft()
         if not self._inflight:
@@ -343,7 +403,7 @@ class LiveSession:
             torch.cuda.current_stream(self.dev).synchronize()
             self._s_down.synchronize()
             for name in ("_h_in", "_d_in", "_scratch", "_maps", "_d_out", "_h_out", "_depth_prev", "_d_mot", "_h_mot",
-                         "_d_ego", "_h_ego", "_ego_scratch"):
+                         "_d_ego", "_h_ego", "_ego_scratch", "_d_conf", "_h_conf"):
                 setattr(self, name, None)
             self._open_done = False
         self._inflight.clear()

@@ -1831,6 +1831,39 @@ def ego_motion(T, depth_prev, K, crop, record, moving, residual=None, scale=1.0,
     return record
 
 
+CONF_OUT_OF_VIEW, CONF_OCCLUDED, CONF_MISMATCH, CONF_INVALID = 1, 2, 4, 128  # CODD_CONF_* of include/codd_hip.h
+
+
+def export_confidence(disp, flags, residual=None, left=None, right=None, crop=None, occ_px=1.0, tau=24.0, std=IMAGENET_STD):
+    """One launch per frame: which pixels of the padded disparity ``disp`` [H,W] (or [1,1,H,W]) to trust, inside the
+    ``crop`` (h, w) (default: the shape of ``flags``).  ``flags`` uint8 [h,w] (caller-owned) gets the CONF_* bits:
+    OUT_OF_VIEW (the match falls left of the right image), OCCLUDED (another pixel of the row lands on the same right
+    column with a disparity more than ``occ_px`` larger), INVALID (disparity not finite or not > 0) and, with the
+    normalised images ``left`` / ``right`` [3,H,W] (or [1,3,H,W]; as preprocess / ingest_pair wrote them with ``std``),
+    MISMATCH (the photometric residual exceeds ``tau`` grey levels); ``residual`` fp32 [h,w] or None gets that residual,
+    NaN where invalid or out of view (include/codd_hip.h, codd_export_confidence)."""
+    lib = _abi.load()
+    _require_gpu(disp)
+    H, W = disp.shape[-2:]
+    h, w = (int(crop[0]), int(crop[1])) if crop is not None else tuple(flags.shape)
+    assert disp.dtype == torch.float32 and disp.is_cuda and disp.is_contiguous() and disp.numel() == H * W
+    assert flags.dtype == torch.uint8 and flags.is_cuda and flags.is_contiguous() and tuple(flags.shape) == (h, w)
+    assert (left is None) == (right is None), "left and right are given together or not at all"
+    for t in (left, right):
+        if t is not None:
+            assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == 3 * H * W
+            assert tuple(t.shape[-3:]) == (3, H, W)
+    if residual is not None:
+        assert left is not None, "residual needs the images"
+        assert residual.dtype == torch.float32 and residual.is_cuda and residual.is_contiguous() and tuple(residual.shape) == (h, w)
+    s = (C.c_float * 3)(*std) if left is not None else None
+    _abi.check(lib.codd_export_confidence(disp.data_ptr(), None if left is None else left.data_ptr(),
+                                          None if right is None else right.data_ptr(), H, W, h, w, s, float(occ_px),
+                                          float(tau), flags.data_ptr(), None if residual is None else residual.data_ptr(),
+                                          _stream()), "export_confidence")
+    return flags
+
+
 def fusion_select(mode, cur, warp, gt=None, K=0.5):
     """mode 'kalman' / 'gt' (ablation fusions).  cur, warp [B,1,H,W]; gt [B,1,hg,wg]."""
     lib = _abi.load()

@@ -580,6 +580,41 @@ int codd_ego_motion(const float* T, const float* depth_prev, int H, int W, int h
                     float cy, float scale, int iters, float delta_px, float tau_px, int min_valid, void* scratch,
                     long long scratch_bytes, float* record, unsigned char* moving, float* residual, void* stream);
 
+/* Live-session stereo confidence: which pixels of the frame's disparity to trust.  The reference has no such output (its
+ * evaluation masks come from ground truth); this replaces the scatter-max per row, the gathers and the dozen element-wise
+ * launches a user writes with torch.  One launch, no allocation, no host synchronisation.
+ * disp [H,W]: the frame's padded disparity; left / right fp32 [3,H,W]: the normalised images exactly as codd_ingest_pair /
+ * codd_preprocess wrote them, given together or not at all; stdv: HOST pointer to the 3 stds of that normalisation (RGB
+ * order), required iff the images are given.  All are read inside the h x w crop only.  Outputs, caller-owned: flags
+ * [h,w] bytes, contiguous, any alignment; residual fp32 [h,w], float alignment, may be NULL and must be NULL without
+ * images.  Nothing outside the crop is read or written.
+ * Per crop pixel (y, x), d = disp[y,x], every operation below one fp32 operation:
+ *   INVALID (128)     d is not finite or not > 0: flags = 128, residual NaN, the pixel takes no further part;
+ *   OUT_OF_VIEW (1)   u = (float)x - d is < 0: flags = 1, residual NaN, the pixel is not splatted;
+ *   splat             f = (int)floorf(u); the pixel offers d to columns f and f + 1 (each only if < w) of its row's
+ *                     right-view z-buffer; zbuf[c] is the largest d offered to column c;
+ *   OCCLUDED (2)      r = (int)floorf(u + 0.5f) (f or f + 1, never w); set iff zbuf[r] > d + occ_px (a pixel never
+ *                     occludes itself: zbuf[r] >= d);
+ *   residual          with images, for every pixel neither invalid nor out of view (occluded ones too): a = u - (float)f,
+ *                     x1 = min(f + 1, w - 1), per channel c: Rv = right[c,y,f] * (1 - a) + right[c,y,x1] * a,
+ *                     e_c = |left[c,y,x] - Rv| * stdv[c]; residual = ((e_0 + e_1) + e_2) * (1/3): grey levels of the 8-bit
+ *                     source; no operation is fused;
+ *   MISMATCH (4)      residual > tau (false for NaN; never set without images).
+ * The flags OR together (6: occluded and mismatched).  Equal inputs give equal bytes: the z-buffer is an integer
+ * maximum over the floats' bits, which does not depend on arrival order.
+ * A workgroup owns a row and keeps its z-buffer and disparities in LDS, 8 bytes per pixel: w <= CODD_CONF_MAX_W = 8192
+ * (64 KiB), CODD_EUNSUPPORTED beyond it.
+ * CODD_EINVAL, before any launch: disp or flags NULL; one image without the other; images without stdv; residual
+ * without images; a non-positive size, h > H or w > W; occ_px negative or NaN; tau NaN. */
+#define CODD_CONF_OUT_OF_VIEW 1
+#define CODD_CONF_OCCLUDED 2
+#define CODD_CONF_MISMATCH 4
+#define CODD_CONF_INVALID 128
+#define CODD_CONF_MAX_W 8192
+int codd_export_confidence(const float* disp, const float* left, const float* right, int H, int W, int h, int w,
+                           const float* stdv, float occ_px, float tau, unsigned char* flags, float* residual,
+                           void* stream);
+
 /* Ablation plug-ins.  codd_fusion_select: mode 0 = KalmanFusion (model/fusion/others.py:124-153; constant
  * gain K = Q/(Q+R), the reference never updates P), mode 1 = GTFusion (:54-86; gt [B,1,hg,wg], zero-padded).
  * cur, warp, out: [B,1,H,W]. */
