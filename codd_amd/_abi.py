@@ -96,6 +96,7 @@ SIGNATURES = {
     "codd_resize_bilinear_add": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _p, _p]),
     "codd_add_relu": (_i, [_p, _p, _ll, _i, _p, _p]),
     "codd_copy_many": (_i, [_p, _p, _p, _i, _p]),
+    "codd_copy": (_i, [_p, _p, _ll, _p]),
     "codd_timestamp": (_i, [_p, _p]),
     "codd_gru_gate_zr": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
     "codd_gru_gate_q": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p]),

@@ -40,7 +40,7 @@ __global__ void resize_bilinear_kernel(const float* __restrict__ in, int C, int 
   } else if (accumulate) {
     v += *o;
   }
-  if (relu) v = fmaxf(v, 0.f);
+  if (relu) v = relu_nan(v);
   *o = v;
 }
 
@@ -70,7 +70,7 @@ __global__ void add_relu_kernel(const float* __restrict__ a, const float* __rest
   long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n) return;
   float v = a[e] + (b ? b[e] : 0.f);
-  if (relu) v = fmaxf(v, 0.f);
+  if (relu) v = relu_nan(v);
   y[e] = v;
 }
 
@@ -119,3 +119,16 @@ extern "C" int codd_copy_many(const float* const* src, float* const* dst, const 
   return CODD_OK;
 }
 
+// The copy for pairs that miss the 16-byte rules above: 32-bit words moved as integers, so that every bit pattern
+// (-0.0, NaN payloads, denormals) arrives as it left.  (add_relu(s, NULL, relu = 0) is s + 0.f: -0.0 becomes +0.0.)
+__global__ void copy_words_kernel(const unsigned* __restrict__ src, unsigned* __restrict__ dst, long long n) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) dst[e] = src[e];
+}
+extern "C" int codd_copy(const float* src, float* dst, long long n, void* stream) {
+  if (!src || !dst || n < 0 || ((uintptr_t)src & 3) || ((uintptr_t)dst & 3)) return CODD_EINVAL;
+  if (n == 0) return CODD_OK;
+  copy_words_kernel<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>((const unsigned*)src, (unsigned*)dst, n);
+  CODD_LAUNCH_CHECK();
+  return CODD_OK;
+}

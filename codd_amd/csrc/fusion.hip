@@ -465,7 +465,9 @@ extern "C" int codd_tepe_metrics(const float* pred, const float* gt, const float
                                  const float* flow_prev, const float* gt_mask, const float* gt2_prev, int B, int H, int W,
                                  int h, int w, float lo, float hi, float bf, double* scratch, double* meters,
                                  void* stream) {
-  if (!pred || !gt || !pred_prev || !gt_prev || !flow_prev || !scratch || !meters || h > H || w > W) return CODD_EINVAL;
+  if (!pred || !gt || !pred_prev || !gt_prev || !flow_prev || !scratch || !meters || h > H || w > W || h < 1 ||
+      w < 1)
+    return CODD_EINVAL;
   const int nblk = 128;
   hipStream_t s = (hipStream_t)stream;
   tepe_partial_kernel<<<dim3(nblk, B), 256, 0, s>>>(pred, gt, pred_prev, gt_prev, flow_prev, gt_mask ? gt_mask : gt,
@@ -621,7 +623,8 @@ __global__ __launch_bounds__(256) void sceneflow_partial_kernel(
     const float dc = dchange[idx];
     if (!(gp > lo && gp < hi && sqrtf(fu * fu + fv * fv) < bf && fabsf(dc) < bf)) continue;
     if (occ && occ[idx]) continue;
-    const float d1 = fminf(fmaxf(bf / pred_prev[idx], 0.f), bf);  // bf / 0 = inf -> bf
+    const float q1 = bf / pred_prev[idx];                                // bf / 0 = inf -> bf
+    const float d1 = q1 != q1 ? q1 : fminf(fmaxf(q1, 0.f), bf);          // torch.clip: a NaN prediction stays a NaN
     const V3 X0 = inv_project(d1, x, y, fx, fy, cx, cy);
     const V3 X1 = se3_act(se3_load(Ts + idx * 7), X0);
     const V3 a = project(X1, fx, fy, cx, cy), c = project(X0, fx, fy, cx, cy);

@@ -71,13 +71,13 @@ __global__ __launch_bounds__(256) void instnorm_apply_kernel(const float* __rest
       float4 v = *(const float4*)(x + base + i);
       v.x = (v.x - mean) * rstd; v.y = (v.y - mean) * rstd; v.z = (v.z - mean) * rstd; v.w = (v.w - mean) * rstd;
       if (res) { const float4 r = *(const float4*)(res + base + i); v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w; }
-      if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+      if (relu) { v.x = relu_nan(v.x); v.y = relu_nan(v.y); v.z = relu_nan(v.z); v.w = relu_nan(v.w); }
       *(float4*)(y + base + i) = v;
     } else {
       for (int c = 0; c < 4 && i + c < HW; ++c) {
         float v = (x[base + i + c] - mean) * rstd;
         if (res) v += res[base + i + c];
-        if (relu) v = fmaxf(v, 0.f);
+        if (relu) v = relu_nan(v);
         y[base + i + c] = v;
       }
     }
@@ -126,8 +126,8 @@ __global__ __launch_bounds__(256) void instnorm_apply_xs_kernel(const float* __r
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     float t = (v[c] - st[c][0]) * st[c][1];
-    if (relu) t = fmaxf(t, 0.f);
-    if (res) { t += r[c]; if (relu2) t = fmaxf(t, 0.f); }
+    if (relu) t = relu_nan(t);
+    if (res) { t += r[c]; if (relu2) t = relu_nan(t); }
     v[c] = t;
     if (y) y[(size_t)(bc0 + c) * HW + i] = t;
   }
@@ -1711,7 +1711,7 @@ __global__ void context_split_kernel(const float* __restrict__ x, int hw, float*
   const long long b = e / (512LL * hw), r = e - b * 512LL * hw;
   const float v = x[e];
   if (r < 128LL * hw) net[b * 128LL * hw + r] = tanhf(v);
-  else inp[b * 384LL * hw + (r - 128LL * hw)] = fmaxf(v, 0.f);
+  else inp[b * 384LL * hw + (r - 128LL * hw)] = relu_nan(v);
 }
 extern "C" int codd_context_split(const float* x, int B, int hw, float* net, float* inp, void* stream) {
   if (!x || !net || !inp) return CODD_EINVAL;

@@ -1478,16 +1478,19 @@ def add_relu(a, b=None, relu=True, out=None):
 def copy_many(pairs):
     """dst.copy_(src) for up to 8 (dst, src) pairs of contiguous fp32 tensors in one kernel launch (a kernel node under
     graph capture: see runtime.FrameRunner._capture); pairs that do not meet the 16-byte rules fall back to one
-    launch each."""
+    codd_copy launch each (a kernel node under capture like the fast path; 32-bit words moved as integers: bit-exact,
+    unlike an add of 0.f, which turns -0.0 into +0.0)."""
     import ctypes as C
     lib = _abi.load()
     fast = []
     for d, s in pairs:
         assert d.numel() == s.numel() and d.is_contiguous() and s.is_contiguous()
+        if s.numel() == 0:  # (an empty tensor's pointer may be NULL, which the entry points reject)
+            continue
         if s.numel() % 4 == 0 and s.data_ptr() % 16 == 0 and d.data_ptr() % 16 == 0:
             fast.append((d, s))
         else:
-            add_relu(s, None, relu=False, out=d)
+            _abi.check(lib.codd_copy(s.data_ptr(), d.data_ptr(), s.numel(), _stream()), "copy")
     for i in range(0, len(fast), 8):
         chunk = fast[i:i + 8]
         n = len(chunk)

@@ -399,6 +399,9 @@ int codd_add_relu(const float* a, const float* b, long long n, int relu, float* 
 /* dst[k][0..n[k]) = src[k][0..n[k]) for k < count <= 8 in ONE launch (the recurrent-state write-back at the end of a
  * captured frame); every n[k] a multiple of 4, every pointer 16-byte aligned. */
 int codd_copy_many(const float* const* src, float* const* dst, const long long* n, int count, void* stream);
+/* dst[0..n) = src[0..n) bit for bit, 32-bit words at any 4-byte alignment, any n >= 0 (the pairs of ops.copy_many that
+ * miss the 16-byte rules of codd_copy_many; a kernel node under graph capture). */
+int codd_copy(const float* src, float* dst, long long n, void* stream);
 
 /* Diagnostics: *slot = the device's constant-rate wall clock (100 MHz ticks) when this one-thread launch runs -- a
  * marker inside a captured frame that does not perturb the replay the way a profiler does (tools/frame_marks.py). */
@@ -459,7 +462,19 @@ int codd_fusion_blend(const float* pred_curr, const float* pred_warp, const floa
                       const float* wr_logit_sig, int B, int H, int W, int ds,
                       float* fused, float* wf_out, float* wr_out, void* stream);
 
-/* On-device disparity metrics (model/codd.py:456-471; utils/metric.py:9-17,40-54): over the mask
+/* The three metric entry points below share two rules.
+ * Batch: the B items of a call are B FRAMES, added to ``meters`` in index order -- one call at B equals B calls at
+ * B = 1 on the items in turn (bit for bit for codd_disp_metrics / codd_tepe_metrics, whose meters receive one mean per
+ * item; up to the fp64 rounding of the sums for codd_sceneflow_metrics).  An item whose mask is empty moves neither its
+ * means nor its count.  This is NOT the joint mean over a batch that a torch restatement fed B > 1 forms.
+ * Nearest warp (codd_tepe_metrics, codd_gt_motion): the source pixel of (x, y) under the flow (fx, fy) is
+ * (rint((float)x + fx), rint((float)y + fy)) -- the fp32 sum rounded half to even -- and it is inside the map when the
+ * ROUNDED value lies in [0, w - 1] x [0, h - 1] (so x + fx = -0.5 rounds to 0 and is inside, (w - 1) + 0.5 is inside when
+ * w - 1 is even).  grid_sample's normalise / un-normalise arithmetic picks a neighbouring pixel at some exact
+ * half-integer coordinates ("Pointwise kernels"); this rule is the exact one and is kept.
+ * All three return CODD_EINVAL for h < 1, w < 1, h > H or w > W.
+ *
+ * On-device disparity metrics (model/codd.py:456-471; utils/metric.py:9-17,40-54): over the mask
  * lo < gt < hi of the crop [0,h) x [0,w) of [B,1,H,W] maps, adds the frame's EPE, its > thr rate and
  * 1 to meters[0..2] (fp64, AverageMeter semantics) when the mask is non-empty.  No host sync.
  * scratch: 3*128*B doubles. */

@@ -457,6 +457,20 @@ def test_instnorm_against_fp64(case):
             for b in range(B):
                 assert torch.equal(ops.instnorm(_items(xd, b), relu=True, res=_items(rd, b)), y[b:b + 1])
     _note("instnorm", case, {"instnorm": top})
+    # a NaN in a plane makes the whole plane NaN, through both ReLUs (torch.relu keeps a NaN; fmaxf(NaN, 0) is 0) and in
+    # both apply kernels; the other planes keep their bits
+    xn = xd.clone()
+    xn[B - 1, 5, h // 2, w // 3] = float("nan")
+    want = torch.zeros(B, Cc, 1, 1, dtype=torch.bool, device=DEV)
+    want[B - 1, 5] = True
+    clean = ops.instnorm(xd, relu=True, res=rd)
+    yn = ops.instnorm(xn, relu=True, res=rd)
+    assert torch.equal(torch.isnan(yn), want.expand_as(yn)) and torch.equal(yn[~want.expand_as(yn)], clean[~want.expand_as(yn)])
+    with _precision("split"):
+        xs = ops.split_buffer(("fp64", "inorm"), B, Cc, h, w, 1, DEV)
+        for relu2 in (False, True):
+            yn = ops.instnorm(xn, relu=True, res=rd, res_relu=relu2, xs_out=xs, want_fp32=True)
+            assert torch.equal(torch.isnan(yn), want.expand_as(yn)), relu2
     top = 0.0
     with _precision("split"):
         for relu, with_res, relu2 in ((True, False, False), (True, True, True), (False, True, False), (True, True, False)):
