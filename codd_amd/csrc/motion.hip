@@ -1348,6 +1348,13 @@ __device__ __forceinline__ bool splat_point(const SplatP& p, int b, int n, float
   return fabsf(*u) < 1e7f && fabsf(*v) < 1e7f;  // also rejects NaN / inf
 }
 
+// d^2 of a point to a pixel centre, ONE written-out evaluation for all three passes: the count and the fill pass must
+// decide coverage alike to the last bit (the lists are exact-size: a pixel counted but not filled leaves a slot the gather
+// pass reads as a point id, one filled but not counted overwrites its neighbour's list), and alpha must be > 0 for every
+// candidate.  fmaf(du, du, dv * dv) is what the compiler's contraction of du * du + dv * dv gave in all three kernels;
+// spelled out, it no longer depends on each instantiation being contracted the same way.
+__device__ __forceinline__ float splat_d2(float du, float dv) { return fmaf(du, du, dv * dv); }
+
 // visits the pixels covered by the point (u, v): f(global pixel index)
 template <typename F>
 __device__ __forceinline__ void splat_cover(const SplatP& p, int b, float u, float v, F f) {
@@ -1361,7 +1368,7 @@ __device__ __forceinline__ void splat_cover(const SplatP& p, int b, float u, flo
       const int xx = bx + ox;
       if ((unsigned)xx >= (unsigned)p.W) continue;
       const float du = u - ((float)xx + 0.5f), dv = v - ((float)yy + 0.5f);
-      if (!(du * du + dv * dv < R2)) continue;
+      if (!(splat_d2(du, dv) < R2)) continue;
       f((size_t)b * p.H * p.W + (size_t)yy * p.W + xx);
     }
   }
@@ -1453,7 +1460,7 @@ __global__ void splat_gather_kernel(const SplatP p) {
     // 16 bytes written by pass 1 instead of re-loading T (28 B) + depth and redoing the SE3 action per candidate
     const float4 q4 = p.uvz[(size_t)b * HW + n];
     const float du = q4.x - ((float)px + 0.5f), dv = q4.y - ((float)py + 0.5f);
-    float cz = q4.z, ca = 1.f - (du * du + dv * dv) / R2;
+    float cz = q4.z, ca = 1.f - splat_d2(du, dv) / R2;
     int cn = n;
     // insertion by carrying the displaced element down the list
 #pragma unroll
@@ -1535,7 +1542,8 @@ extern "C" int codd_splat(const float* T, const float* depth, int HT, int WT, in
   if (!T || !depth || !out || !scratch || ((uintptr_t)scratch & 15) || !(radius > 0.f) || CA < 0 || CB < 0 ||
       (CA > 0 && !featA) || (CB > 0 && !featB))
     return CODD_EINVAL;
-  if (oy + ds * (H - 1) >= HT || ox + ds * (W - 1) >= WT) return CODD_EINVAL;
+  if (B < 1 || H < 1 || W < 1 || HT < 1 || WT < 1 || ds < 1 || oy < 0 || ox < 0) return CODD_EINVAL;
+  if ((long long)oy + (long long)ds * (H - 1) >= HT || (long long)ox + (long long)ds * (W - 1) >= WT) return CODD_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   SplatP p;
   p.T = T; p.depth = depth; p.HT = HT; p.WT = WT; p.oy = oy; p.ox = ox; p.ds = ds;

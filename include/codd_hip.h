@@ -365,7 +365,27 @@ int codd_subsample(const float* in, int B, int H, int W, int oy, int ox, int ste
  *   disp = bf/(z+1e-5), > W -> 0 (motion.py:190-193).
  * scratch: 16-byte aligned, codd_splat_scratch(B, H, W, radius) ints (per-pixel counters / list offsets, EXACT-SIZE
  * candidate lists -- a point covers at most (2 ceil(R) + 1)^2 pixel centres, R = radius min(H,W) / (2H) px, which
- * bounds them: no candidate is ever dropped -- and one float4 (u, v, z, valid) per source point). */
+ * bounds them: no candidate is ever dropped -- and one float4 (u, v, z, valid) per source point).
+ * CODD_EINVAL: a NULL T / depth / out / scratch, a missing feature pointer, a scratch that is not 16-byte aligned,
+ * radius not > 0, B, H, W, HT, WT or ds < 1, oy or ox < 0, a sample outside the field (oy + ds (H - 1) >= HT,
+ * ox + ds (W - 1) >= WT); nothing is launched then.  codd_splat_scratch returns -1 for sizes < 1 or radius not > 0.
+ *
+ * Scratch layout, in ints, once the launches have completed; n = B H W, bound = (2 ceil(R) + 1)^2, R evaluated in
+ * fp32, nhead = (3 n + 4 + 3) & ~3, nlist = (n bound + 3) & ~3, codd_splat_scratch = nhead + nlist + 4 n:
+ *   [0, n)                  cnt:  candidates of output pixel (b, y, x) at (b H + y) W + x: the valid points of item b
+ *                                 with d^2 < R^2 to the pixel's centre (x + 0.5, y + 0.5);
+ *   [n, 2 n)                off:  where the pixel's list starts in `list` (any value where cnt is 0);
+ *   [2 n, 3 n)              cur:  entries the fill pass wrote into the pixel's list: equal to cnt;
+ *   [3 n]                   cursor: entries in `list` = the sum of cnt; [3 n + 1, 3 n + 4) are 0; the rest of the
+ *                                 head up to nhead is not written;
+ *   [nhead, nhead + nlist)  list: the ranges [off, off + cnt) of the pixels with cnt > 0 are disjoint and tile
+ *                                 [0, cursor) (in no particular order); an entry is the index y W + x of a source point
+ *                                 of the pixel's own item, each point at most once per list, in no particular order;
+ *                                 entries from cursor on are not written;
+ *   [nhead + nlist, + 4 n)  uvz:  per source point (b H + y) W + x four floats: the projected u, v, z = (T X0).z and
+ *                                 valid = 1.f (z > 0, |u| < 1e7, |v| < 1e7) or 0.f (u, v then meaningless).
+ * The count and the fill pass decide coverage with the same fp32 expression on the same stored (u, v); the gather
+ * pass reads exactly these lists. */
 long long codd_splat_scratch(int B, int H, int W, float radius);
 int codd_splat(const float* T, const float* depth, int HT, int WT, int oy, int ox, int ds,
                const float* featA, int CA, const float* featB, int CB, int with_flow,
