@@ -48,6 +48,141 @@ __device__ __forceinline__ const float* view_ptr(const codd_view& v, int b, int 
   return v.ptr + ((size_t)b * v.ctot + v.coff + c) * (size_t)hw;
 }
 
+// Epilogue shared by conv_mfma_kernel and conv_quad_body: bias, res1, res2, activation, post, store -- in phases.  A
+// value-at-a-time loop (load bias, load res1, ..., store, next value) costs one memory round trip per LOAD: the operand
+// and output pointers are kernel arguments, so a store may alias the next load and the compiler keeps program order and
+// drains vmcnt (which on gfx9 also counts the previous store) before every use.  Here a batch of accumulator blocks
+//   (a) gets its predicates and pixel offsets,
+//   (b) issues every bias / res1 / res2 / post load into registers -- before any store of the batch,
+//   (c) waits once (at the first use),
+//   (d) applies ((acc + bias) + res1) + res2 -> act_apply -> + post per value: the order of the value-at-a-time loop, so
+//       every output element keeps its bits,
+//   (e) stores.
+// A load is issued exactly where that loop issued it: co < cout_eff, oy < Hout, ox < Wout, operand present; no other
+// address is formed.  Aliasing contract (include/codd_hip.h, codd_conv_params): an operand may be the output tensor
+// itself element for element -- the lane that writes out[c][pixel] is the only one that reads operand[c][pixel], and
+// it reads before it writes.
+// A batch is BLK of the lane's NPB * MB accumulator blocks (4 values each, block q = m * NPB + a: the pixel blocks of
+// one channel block are neighbours, so its channel base addresses die early): up to 4 blocks, i.e. the whole lane of
+// the 4 x 16 tiles with 16 / 32 / 64 channels per group -- 2 blocks where the staging registers of the K loop (DEAD of
+// them, dead by now) do not cover the 4 x 16 operand registers of 4 blocks -- so that no instantiation needs more
+// registers than its K loop (same occupancy, no scratch: profiles/conv_fp32_epilogue_resources.txt).
+template <int NPB, int MB, int DEAD>
+__device__ __forceinline__ void conv_epilogue(const ConvK& k, const f32x4 (&acc)[NPB][MB], int b, int cog, int ty, int tx,
+                                              int wave, int g, int j) {
+  const codd_conv_params& p = k.p;
+  constexpr int XB = NPB >= 2 ? 2 : 1;
+  constexpr int RPW = NPB / XB;
+  constexpr int NBLK = NPB * MB;
+  constexpr int BLK = NBLK <= 2 ? NBLK : (DEAD >= 48 ? 4 : 2);  // blocks per batch
+  static_assert(NBLK % BLK == 0, "batch");
+  const int hwout = p.Hout * p.Wout;
+#ifdef CONV_NO_EPILOGUE
+  {  // dev ablation: one store per lane keeps the accumulators alive
+    float s_ = 0.f;
+#pragma unroll
+    for (int a = 0; a < NPB; ++a)
+#pragma unroll
+      for (int m = 0; m < MB; ++m) s_ += acc[a][m][0] + acc[a][m][1] + acc[a][m][2] + acc[a][m][3];
+    const int oy = ty * k.th + wave * RPW, ox = tx * k.tw + j;
+    const int co = cog * MB * 16 + 4 * g;
+    if (oy < p.Hout && ox < p.Wout && co < k.cout_eff && p.store_mode == 0)
+      p.out[((size_t)b * p.out_ctot + p.out_coff + co) * (size_t)hwout + oy * p.Wout + ox] = s_;
+    return;
+  }
+#endif
+  bool cok[MB][4], pok[NPB], anyp = false;  // channel / pixel predicates
+  int oy[NPB], ox[NPB];
+#pragma unroll
+  for (int m = 0; m < MB; ++m)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) cok[m][r] = (cog * MB + m) * 16 + 4 * g + r < k.cout_eff;
+#pragma unroll
+  for (int a = 0; a < NPB; ++a) {
+    oy[a] = ty * k.th + wave * RPW + a / XB;
+    ox[a] = tx * k.tw + (a % XB) * 16 + j;
+    pok[a] = oy[a] < p.Hout && ox[a] < p.Wout;
+    anyp |= pok[a];
+  }
+  if (p.store_mode == 0) {
+    int pix[NPB];
+#pragma unroll
+    for (int a = 0; a < NPB; ++a) pix[a] = oy[a] * p.Wout + ox[a];
+#pragma unroll
+    for (int q0 = 0; q0 < NBLK; q0 += BLK) {
+      float bv[BLK][4], r1[BLK][4], r2[BLK][4], po[BLK][4];
+#define CONV_EPI_LOAD(DST, VIEW)                                                         \
+  _Pragma("unroll") for (int i = 0; i < BLK; ++i)                                        \
+  _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                        \
+    const int a = (q0 + i) % NPB, m = (q0 + i) / NPB;                                    \
+    DST[i][r] = 0.f;                                                                     \
+    if (VIEW.ptr && pok[a] && cok[m][r])                                                 \
+      DST[i][r] = view_ptr(VIEW, b, (cog * MB + m) * 16 + 4 * g + r, hwout)[pix[a]];     \
+  }
+#pragma unroll
+      for (int i = 0; i < BLK; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int a = (q0 + i) % NPB, m = (q0 + i) / NPB;
+          bv[i][r] = 0.f;
+          if (p.bias && pok[a] && cok[m][r]) bv[i][r] = p.bias[(cog * MB + m) * 16 + 4 * g + r];
+        }
+      CONV_EPI_LOAD(r1, p.res1)
+      CONV_EPI_LOAD(r2, p.res2)
+      CONV_EPI_LOAD(po, p.post)
+#undef CONV_EPI_LOAD
+      float v[BLK][4];
+#pragma unroll
+      for (int i = 0; i < BLK; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int a = (q0 + i) % NPB, m = (q0 + i) / NPB;
+          float t = acc[a][m][r];
+          if (p.bias) t += bv[i][r];
+          if (p.res1.ptr) t += r1[i][r];
+          if (p.res2.ptr) t += r2[i][r];
+          t = act_apply(t, p.act, (cog * MB + m) * 16 + 4 * g + r);
+          if (p.post.ptr) t += po[i][r];
+          v[i][r] = t;
+        }
+#pragma unroll
+      for (int i = 0; i < BLK; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int a = (q0 + i) % NPB, m = (q0 + i) / NPB;
+          if (pok[a] && cok[m][r])
+            p.out[((size_t)b * p.out_ctot + p.out_coff + (cog * MB + m) * 16 + 4 * g + r) * (size_t)hwout + pix[a]] = v[i][r];
+        }
+    }
+  } else {  // ConvTranspose2d k=2 s=2: co = (a2*2+b2)*Cout + c; bias only.  One batch per channel block.
+    const int W2 = 2 * p.Wout;
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      int cq[4], cc[4];
+      float bv[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int co = (cog * MB + m) * 16 + 4 * g + r;
+        cq[r] = co / p.Cout;
+        cc[r] = co - cq[r] * p.Cout;
+        bv[r] = 0.f;
+        if (p.bias && anyp && cok[m][r]) bv[r] = p.bias[cc[r]];
+      }
+#pragma unroll
+      for (int a = 0; a < NPB; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (!pok[a] || !cok[m][r]) continue;
+          float t = acc[a][m][r];
+          if (p.bias) t += bv[r];
+          t = act_apply(t, p.act, cc[r]);
+          p.out[((size_t)b * p.out_ctot + p.out_coff + cc[r]) * (size_t)(4 * hwout) +
+                (size_t)(2 * oy[a] + (cq[r] >> 1)) * W2 + 2 * ox[a] + (cq[r] & 1)] = t;
+        }
+    }
+  }
+}
+
 // Staging: a chunk (CK input channels of the halo tile + the matching packed weights) is fetched
 // with 16-byte global loads into REGISTERS right before the MFMA phase of the previous chunk and
 // written to LDS after it (issue early / write late), so that HBM/L2 latency overlaps the matrix
@@ -180,39 +315,7 @@ __global__ __launch_bounds__(NW * 64) void conv_mfma_kernel(const ConvK k) {
     }
   }
 
-  // epilogue
-  const int hwout = p.Hout * p.Wout;
-#pragma unroll
-  for (int a = 0; a < NPB; ++a) {
-    const int oy = ty * k.th + wave * RPW + a / XB;
-    const int ox = tx * k.tw + (a % XB) * 16 + j;
-    if (oy >= p.Hout || ox >= p.Wout) continue;
-    const int pix = oy * p.Wout + ox;
-#pragma unroll
-    for (int m = 0; m < MB; ++m) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int co = (cog * MB + m) * 16 + 4 * g + r;
-        if (co >= k.cout_eff) continue;
-        float v = acc[a][m][r];
-        if (p.store_mode == 0) {
-          if (p.bias) v += p.bias[co];
-          if (p.res1.ptr) v += view_ptr(p.res1, b, co, hwout)[pix];
-          if (p.res2.ptr) v += view_ptr(p.res2, b, co, hwout)[pix];
-          v = act_apply(v, p.act, co);
-          if (p.post.ptr) v += view_ptr(p.post, b, co, hwout)[pix];
-          p.out[((size_t)b * p.out_ctot + p.out_coff + co) * (size_t)hwout + pix] = v;
-        } else {  // ConvTranspose2d k=2 s=2: co = (a2*2+b2)*Cout + c
-          const int q = co / p.Cout, c = co - q * p.Cout;
-          if (p.bias) v += p.bias[c];
-          v = act_apply(v, p.act, c);
-          const int W2 = 2 * p.Wout;
-          p.out[((size_t)b * p.out_ctot + p.out_coff + c) * (size_t)(4 * hwout) +
-                (size_t)(2 * oy + (q >> 1)) * W2 + 2 * ox + (q & 1)] = v;
-        }
-      }
-    }
-  }
+  conv_epilogue<NPB, MB, 4 * WREG + 4 * IREG>(k, acc, b, cog, ty, tx, wave, g, j);
 }
 
 // ---- instantiation lists (X(NW, NPB, MB, WREG, IREG)) -----------------------------------------------

@@ -145,39 +145,7 @@ __device__ __forceinline__ void conv_quad_body(const ConvK& k, int bid, float* s
 #undef QUAD_ISSUE
 #undef QUAD_COMMIT
 
-  // epilogue (identical to conv_mfma_kernel)
-  const int hwout = p.Hout * p.Wout;
-#pragma unroll
-  for (int a = 0; a < NPB; ++a) {
-    const int oy = ty * k.th + wave * RPW + a / XB;
-    const int ox = tx * k.tw + (a % XB) * 16 + j;
-    if (oy >= p.Hout || ox >= p.Wout) continue;
-    const int pix = oy * p.Wout + ox;
-#pragma unroll
-    for (int m = 0; m < MB; ++m) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int co = (cog * MB + m) * 16 + 4 * g + r;
-        if (co >= k.cout_eff) continue;
-        float v = acc[a][m][r];
-        if (p.store_mode == 0) {
-          if (p.bias) v += p.bias[co];
-          if (p.res1.ptr) v += view_ptr(p.res1, b, co, hwout)[pix];
-          if (p.res2.ptr) v += view_ptr(p.res2, b, co, hwout)[pix];
-          v = act_apply(v, p.act, co);
-          if (p.post.ptr) v += view_ptr(p.post, b, co, hwout)[pix];
-          p.out[((size_t)b * p.out_ctot + p.out_coff + co) * (size_t)hwout + pix] = v;
-        } else {
-          const int q = co / p.Cout, c = co - q * p.Cout;
-          if (p.bias) v += p.bias[c];
-          v = act_apply(v, p.act, c);
-          const int W2 = 2 * p.Wout;
-          p.out[((size_t)b * p.out_ctot + p.out_coff + c) * (size_t)(4 * hwout) +
-                (size_t)(2 * oy + (q >> 1)) * W2 + 2 * ox + (q & 1)] = v;
-        }
-      }
-    }
-  }
+  conv_epilogue<NPB, MB, 4 * WREG + 16 * QREG>(k, acc, b, cog, ty, tx, wave, g, j);  // (shared with conv_mfma_kernel: conv_kernel.h)
 }
 
 template <int NW, int NPB, int MB, int WREG, int QREG>

@@ -105,6 +105,14 @@ typedef struct codd_xs_view {
  * `wpacked` is the weight tensor re-laid-out by codd_conv2d_pack_weights for (mb, ck).
  * store_mode 1 = ConvTranspose2d(k=2, s=2) expressed as a 1x1 conv with 4*Cout outputs
  * (co' = (a*2+b)*Cout + co is scattered to out[co][2y+a][2x+b]).
+ *
+ * Aliasing contract of the epilogue operands: res1, res2 or post MAY be the output tensor itself, element for
+ * element (same buffer, same ctot and coff as out / out_ctot / out_coff; the ConvGRU's gate 3 runs with out = post):
+ * the lane that writes out[b][co][y][x] is the only one that reads operand[b][co][y][x], and it reads before it writes.
+ * The kernels issue ALL operand loads of a batch of output elements before that batch's first store (conv_kernel.h
+ * conv_epilogue), so nothing else is allowed: an operand whose elements overlap those of `out` at any OTHER offset (a shifted view, an
+ * overlapping channel range under another coff, a different batch stride), or an input (in0 / in1 / xs) that overlaps `out`,
+ * gives undefined results.  `bias` and `wpacked` never alias `out`.
  * --------------------------------------------------------------------------------------------- */
 typedef struct {
   codd_view in0, in1;
