@@ -499,7 +499,15 @@ class RAFT3D(ops.RuntimeState, nn.Module):
             torch.cuda.current_stream(dev).wait_stream(self._side[0] if key == "fmap" else self._side[1])
         return pend.pop(key)
 
-    def forward(self, image_curr, depth_prev, depth_curr, intrinsics, state, outputs, iters=12, train_mode=False):
+    def forward(self, image_curr, depth_prev, depth_curr, intrinsics, state, outputs, iters=12, train_mode=False,
+                trace=None):
+        """``trace``: None (the product: no launch, sync or allocation on its account), or a list that receives the
+        update loop's state as CLONES (tests/test_gpu_raft_loop_fp64.py; never passed by FrameRunner or under graph
+        capture): first one dict of the loop's inputs -- fmap_prev, fmap_curr, net [B,128,h,w], inp [B,384,h,w], d1, d2
+        [B,h,w], K8 -- then one dict per iteration: ``T`` [B,h,w,7] after the Gauss-Newton step, ``net`` the hidden state as
+        fp32 NCHW (read back from the channel-quad buffer where the gates are convolution epilogues), ``weight``
+        [B,3,h,w] as the step returned it, and on the last iteration ``mask`` [B,576,h,w] (after the join of its
+        fork)."""
         dev = image_curr.device
         if "memory" not in state:
             fm, ni = self._join("fmap", dev), self._join("netinp", dev)
@@ -530,6 +538,10 @@ class RAFT3D(ops.RuntimeState, nn.Module):
         mask = weight = None
         zr = pl["zr"] if pl is not None else None
         cxs, mxs = self.update_block.input_buffers(net)
+        if trace is not None:
+            trace.append(dict(fmap_prev=fmap_prev.clone(), fmap_curr=fmap_curr.clone(), net=net.clone(),
+                              inp=(inp.nchw() if isinstance(inp, ops.C4Tensor) else inp).clone(), d1=d1.clone(),
+                              d2=d2.clone(), K8=list(K8)))
         for it in range(iters):
             # projection + pyramid lookup, one launch; in the split-bf16 modes its results are written straight into
             # the encoder convolutions' input tensors (corr = minfo = None then)
@@ -540,7 +552,13 @@ class RAFT3D(ops.RuntimeState, nn.Module):
                 weight = ops.se3_gn_step_heads(T, hid, *self.update_block.head_matrix(), xyz, d1, K8, radius=32)
             else:
                 ops.se3_gn_step(T, ae, xyz, delta, weight, d1, K8, radius=32)
+            if trace is not None:
+                ub = self.update_block
+                trace.append(dict(T=T.clone(), net=ub._h4c[1].nchw() if ub._fused_now else net.clone(),
+                                  weight=weight.clone()))
         self.update_block._forks(dev)[0].join()  # the mask head's 1x1 convolution (forked beside the last Gauss-Newton step)
+        if trace is not None:
+            trace[-1]["mask"] = mask.clone()
         T_up, outputs["weight"] = ops.cvx_upsample_se3_weight(T, weight.contiguous(), mask)  # one pass over the mask
         outputs["Ts"] = T_up
         # reference raft3d.py:268-270: the induced 2-D flow + inverse-depth change of the up-sampled field
