@@ -56,6 +56,19 @@ def roll(owner, key, specs, residual=False):
     return ent[1]
 
 
+def _clones(**tensors):
+    """The named tensors / Slices as contiguous CLONES made on the current stream."""
+    return {k: (v.tensor() if isinstance(v, Slice) else v).clone(memory_format=torch.contiguous_format)
+            for k, v in tensors.items()}
+
+
+def _rec(trace, stage, level=None, **tensors):
+    """Append one trace entry (``HITNetMF.stereo_matching(trace=[...])``) and return it: clones made on the current
+    stream, i.e. the stream the stage ran on, at the point of production (a stage adds later results to its entry)."""
+    trace.append(dict(stage=stage, level=level, **_clones(**tensors)))
+    return trace[-1]
+
+
 def cv(m, x, x2=None, act="none", **kw):
     """Run nn.Conv2d ``m`` through the HIP conv kernel using the module's own geometry."""
     return ops.conv2d(x, packed(m), x2=x2, stride=tuple(m.stride), pad=tuple(m.padding), dil=tuple(m.dilation),
@@ -97,9 +110,10 @@ class HITUNet(nn.Module):
         self.merge2 = _merge(32, 16)
         self.merge1 = _merge(32, 16)
 
-    def stages(self, x):
+    def stages(self, x, trace=None):
         """Generator over the feature pyramid in production order (1/16, 1/8, 1/4, 1/2, 1/1): a consumer may use the
-        coarse scales while the decoder still runs (HITNetMF.stereo_matching, pipelined schedule)."""
+        coarse scales while the decoder still runs (HITNetMF.stereo_matching, pipelined schedule).  ``trace``: see
+        HITNetMF.stereo_matching (entries "enc" 0..3: the encoder skips, "fea" 0..4: the yielded scales)."""
         def seq(s, t):
             for m in s:
                 if isinstance(m, nn.Conv2d):
@@ -120,12 +134,12 @@ class HITUNet(nn.Module):
             t = cv(merge[2], t, act="lrelu")
             return cv(merge[4], t, act="lrelu")
 
-        yield from self._stages(x, seq, up_merge)
+        yield from self._stages(x, seq, up_merge, trace)
 
-    def forward(self, x):
-        return list(self.stages(x))
+    def forward(self, x, trace=None):
+        return list(self.stages(x, trace))
 
-    def _stages(self, x, seq, up_merge):
+    def _stages(self, x, seq, up_merge, trace=None):
         x0 = seq(self.conv1, x)
         x1 = seq(self.down1, x0)
         x2 = seq(self.down2, x1)
@@ -133,14 +147,18 @@ class HITUNet(nn.Module):
         x4 = seq(self.down4[0], x3)
         x4 = cv(self.down4[1], x4, act="lrelu")
         x4 = cv(self.down4[3], x4, act="lrelu")
+        if trace is not None:
+            for j, t in enumerate((x0, x1, x2, x3)):
+                _rec(trace, "enc", j, enc=t)
+            _rec(trace, "fea", 0, fea=x4)
         yield x4
-        u4 = up_merge(self.up4, self.merge4, x3, x4)
-        yield u4
-        u3 = up_merge(self.up3, self.merge3, x2, u4)
-        yield u3
-        u2 = up_merge(self.up2, self.merge2, x1, u3)
-        yield u2
-        yield up_merge(self.up1, self.merge1, x0, u2)
+        u = x4
+        for i, (up, merge, skip) in enumerate(((self.up4, self.merge4, x3), (self.up3, self.merge3, x2),
+                                               (self.up2, self.merge2, x1), (self.up1, self.merge1, x0)), 1):
+            u = up_merge(up, merge, skip, u)
+            if trace is not None:  # (the body of a generator runs on the stream of the next() that resumes it)
+                _rec(trace, "fea", i, fea=u)
+            yield u
 
 
 # ------------------------------------------------------------------------------------- tile init
@@ -171,9 +189,10 @@ class TileInitialization(ops.RuntimeState, nn.Module):
         for name, c in zip(_LEVELS, (17, 17, 33, 25, 25)):
             setattr(self, f"tile_fea_dscrpt{name}", nn.Sequential(nn.Conv2d(c, 13, 1), _lrelu()))
 
-    def init_level(self, lvl, fl, fr, feat):
+    def init_level(self, lvl, fl, fr, feat, trace=None):
         """One scale: tile features of both views, cost-volume arg-min, tile descriptor -> the 16-channel hypothesis
-        Slice at the head of the aug-hypothesis buffer (``feat``: fea_l[lvl - 2] for lvl >= 2)."""
+        Slice at the head of the aug-hypothesis buffer (``feat``: fea_l[lvl - 2] for lvl >= 2).  ``trace``: entry
+        "init" of this level: tl, tr (after both convolutions), cost, hyp."""
         name = _LEVELS[lvl]
         tc = getattr(self, f"tile_conv{name}")
         pc0, pc1 = packed(tc[0]), packed(tc[2])
@@ -192,14 +211,16 @@ class TileInitialization(ops.RuntimeState, nn.Module):
         ops.tile_costvol_argmin(tl, tr, self.maxdisp // (16 >> lvl), cost, Slice(aug, 0, 3))
         feat = tl if feat is None else feat
         cv(getattr(self, f"tile_fea_dscrpt{name}")[0], cost, x2=feat, act="lrelu", out=Slice(aug, 3, 13))
+        if trace is not None:
+            _rec(trace, "init", lvl, tl=tl, tr=tr, cost=cost, hyp=Slice(aug, 0, 16))
         return Slice(aug, 0, 16)
 
-    def forward(self, fea_l, fea_r):
+    def forward(self, fea_l, fea_r, trace=None):
         """-> [None, hyps]: the cost volumes are not materialised at inference (the reference only
         consumes them in the training loss, hitnet.py:84-85).  hyps[l] is a 16-channel Slice at
         the head of the aug-hypothesis buffer TilePropagation consumes (32 ch at 1/16, else 64)."""
         def level(lvl):
-            return self.init_level(lvl, fea_l[lvl], fea_r[lvl], None if lvl < 2 else fea_l[lvl - 2])
+            return self.init_level(lvl, fea_l[lvl], fea_r[lvl], None if lvl < 2 else fea_l[lvl - 2], trace)
 
         # the five scales are independent 6-launch chains (the four coarse ones ~10 us launches that leave the chip
         # idle): the coarse scales on side streams beside the finest one
@@ -218,7 +239,8 @@ class TileInitialization(ops.RuntimeState, nn.Module):
             return [None, coarse + fine]
         if FORK_INIT_LEVELS and not ops.Fork.serial and getattr(self, "fork_streams", True):
             fk = self.__dict__.get("_fk")
-            if fk is None or fk.dev != fea_l[0].device:
+            # (a fork kept from the one-branch schedule above has ONE side stream: not enough for this one)
+            if fk is None or fk.dev != fea_l[0].device or len(fk.streams) < n - 1:
                 fk = self.__dict__["_fk"] = ops.Fork(fea_l[0].device, n - 1)
             hyps = [fk.run(lvl, level, lvl) for lvl in range(n - 1)] + [level(n - 1)]
             fk.join()
@@ -267,14 +289,23 @@ class TileUpdate0(nn.Module):
         self.resblock1 = _resblock(32)
         self.lastconv = nn.Conv2d(hid_c, out_c, 3, 1, 1)
 
-    def forward(self, fl, fr, hyp):
+    def forward(self, fl, fr, hyp, trace=None):
+        """``trace``: entry "update" of level 0: aug (the 32-channel buffer after ``decrease``), cvc (the same
+        ``decrease`` convolution into a tensor of its own), upd (the raw ``lastconv`` output: the product only forms it
+        inside the epilogue that adds the hypothesis, so this is one more launch), hyp (the result)."""
         aug = hyp.buf  # [hyp 16 | local cv 16]
         w, _ = ops.tile_warp_cost(fl, fr, hyp)
         cv(self.decrease[0], w, act="lrelu", out=Slice(aug, 16, 16))
+        if trace is not None:
+            e = _rec(trace, "update", 0, aug=aug)
+            e["cvc"] = cv(self.decrease[0], w, act="lrelu")
         t = cv(self.conv0[0], aug, act="lrelu")
         t = self.resblock0[0].run(t)
         t = self.resblock1[0].run(t)
-        return [cv(self.lastconv, t, res1=hyp, act="relu_ch0")]
+        out = cv(self.lastconv, t, res1=hyp, act="relu_ch0")
+        if trace is not None:
+            e.update(upd=cv(self.lastconv, t), **_clones(hyp=out))
+        return [out]
 
 
 class TileUpdate(nn.Module):
@@ -288,21 +319,31 @@ class TileUpdate(nn.Module):
         self.resblock1 = _resblock(32)
         self.lastconv = nn.Conv2d(32, 34, 3, 1, 1)
 
-    def forward(self, fl, fr, hyp, prev):
+    def forward(self, fl, fr, hyp, prev, trace=None, level=None):
+        """``trace``: entry "update" of ``level``: up (the up-sampled previous hypothesis, cloned as soon as it is
+        written), aug (the 64-channel buffer after both ``decrease`` convolutions), cvc / cvp (the same two
+        convolutions into tensors of their own: two more launches), upd (the raw 34-channel ``lastconv`` output), hyp."""
         aug = hyp.buf  # [cur 16 | cv_cur 16 | up_prev 16 | cv_prev 16]
         up = Slice(aug, 32, 16)
         ops.hyp_upsample(prev, 2.0, up)
+        if trace is not None:
+            e = _rec(trace, "update", level, up=up)
         w0, w1 = ops.tile_warp_cost(fl, fr, hyp, up)
         with ops.deferred_convs():  # (two independent 1x1 convolutions: one multi-job launch, same bits)
             cv(self.decrease[0], w0, act="lrelu", out=Slice(aug, 16, 16))
             cv(self.decrease[0], w1, act="lrelu", out=Slice(aug, 48, 16))
+        if trace is not None:
+            e.update(cvc=cv(self.decrease[0], w0, act="lrelu"), cvp=cv(self.decrease[0], w1, act="lrelu"), **_clones(aug=aug))
         t = cv(self.conv0[0], aug, act="lrelu")
         t = self.resblock0[0].run(t)
         t = self.resblock1[0].run(t)
         upd = cv(self.lastconv, t)
         B, _, h, w = upd.shape
         out = torch.empty(B, 16, h, w, device=upd.device, dtype=torch.float32)
-        return [ops.hyp_select(upd, hyp, up, out)]
+        ops.hyp_select(upd, hyp, up, out)
+        if trace is not None:
+            e.update(_clones(upd=upd, hyp=out))
+        return [out]
 
 
 class PostTileUpdate(nn.Module):
@@ -370,13 +411,20 @@ class TilePropagation(nn.Module):
         self.tile_update5 = PostTileUpdate(32, 16, 32, 4)
         self.tile_update6 = FinalTileUpdate(32, 3, 16, 2)
 
-    def forward(self, fea_l, fea_r, init):
-        h = self.tile_update0(fea_l[0], fea_r[0], init[0])[0]
+    def forward(self, fea_l, fea_r, init, trace=None):
+        h = self.tile_update0(fea_l[0], fea_r[0], init[0], trace)[0]
         for i, upd in enumerate((self.tile_update1, self.tile_update2, self.tile_update3, self.tile_update4), 1):
-            h = upd(fea_l[i], fea_r[i], init[i], h)[0]
-        r1 = self.tile_update4_1(fea_l[2], h)
-        r05 = self.tile_update5(fea_l[3], _up1(r1))
-        return self.tile_update6(fea_l[4], _up1(r05))
+            h = upd(fea_l[i], fea_r[i], init[i], h, trace, i)[0]
+        return self.post(fea_l, h, trace)
+
+    def post(self, fea_l, h, trace=None):
+        """The three refinement steps behind tile_update4 (fea_l: a list or a callable level -> left features).
+        ``trace``: entries "r1", "up_r1", "r05", "up_r05", "pred_disp", each with ``out``."""
+        L = fea_l if callable(fea_l) else fea_l.__getitem__
+        rec = (lambda k, t: t) if trace is None else (lambda k, t: (_rec(trace, k, out=t), t)[1])
+        r1 = rec("r1", self.tile_update4_1(L(2), h))
+        r05 = rec("r05", self.tile_update5(L(3), rec("up_r1", _up1(r1))))
+        return rec("pred_disp", self.tile_update6(L(4), rec("up_r05", _up1(r05))))
 
 
 @register
@@ -394,7 +442,7 @@ class HITNetMF(ops.RuntimeState, nn.Module):
     def extract_feat(self, img):
         return self.backbone(img)
 
-    def _stereo_matching_pipelined(self, left_img, right_img):
+    def _stereo_matching_pipelined(self, left_img, right_img, trace=None):
         """Two-stream schedule of the same launches: the coarse-to-fine propagation only needs scale i's features and
         initialisation at step i, and the finest initialisation only the end of the U-Net decoder.  A side stream runs
         decoder scales 1/4, 1/2, 1/1 and the finest initialisation; the caller's stream runs the coarse
@@ -402,7 +450,7 @@ class HITNetMF(ops.RuntimeState, nn.Module):
         scale-by-scale (events) -- ONE branch, one join."""
         B, dev = left_img.shape[0], left_img.device
         ti, tu = self.tile_init, self.tile_update
-        g = self.backbone.stages(ops.batch_pair(left_img, right_img))
+        g = self.backbone.stages(ops.batch_pair(left_img, right_img), trace)
         feas = [next(g), next(g)]  # 1/16, 1/8 (on the caller's stream)
         L, R = (lambda i: feas[i][:B]), (lambda i: feas[i][B:])
         rt = self.__dict__.get("_pipe")
@@ -415,40 +463,48 @@ class HITNetMF(ops.RuntimeState, nn.Module):
         with torch.cuda.stream(side):
             feas.append(next(g))
             if PIPE_INIT_SIDE >= 2:
-                hyp2 = ti.init_level(2, L(2), R(2), L(0))
+                hyp2 = ti.init_level(2, L(2), R(2), L(0), trace)
             ev3.record(side)
             feas.append(next(g))
             if PIPE_INIT_SIDE >= 1:
-                hyp3 = ti.init_level(3, L(3), R(3), L(1))
+                hyp3 = ti.init_level(3, L(3), R(3), L(1), trace)
             ev2.record(side)
             feas.append(next(g))
-            hyp4 = ti.init_level(4, L(4), R(4), L(2))
-        hyp0, hyp1 = ti.init_level(0, L(0), R(0), None), ti.init_level(1, L(1), R(1), None)
-        h = tu.tile_update0(L(0), R(0), hyp0)[0]
-        h = tu.tile_update1(L(1), R(1), hyp1, h)[0]
+            hyp4 = ti.init_level(4, L(4), R(4), L(2), trace)
+        hyp0, hyp1 = ti.init_level(0, L(0), R(0), None, trace), ti.init_level(1, L(1), R(1), None, trace)
+        h = tu.tile_update0(L(0), R(0), hyp0, trace)[0]
+        h = tu.tile_update1(L(1), R(1), hyp1, h, trace, 1)[0]
         cur.wait_event(ev3)
-        h = tu.tile_update2(L(2), R(2), hyp2 if hyp2 is not None else ti.init_level(2, L(2), R(2), L(0)), h)[0]
+        h = tu.tile_update2(L(2), R(2), hyp2 if hyp2 is not None else ti.init_level(2, L(2), R(2), L(0), trace), h, trace, 2)[0]
         cur.wait_event(ev2)
-        h = tu.tile_update3(L(3), R(3), hyp3 if hyp3 is not None else ti.init_level(3, L(3), R(3), L(1)), h)[0]
+        h = tu.tile_update3(L(3), R(3), hyp3 if hyp3 is not None else ti.init_level(3, L(3), R(3), L(1), trace), h, trace, 3)[0]
         cur.wait_stream(side)
-        h = tu.tile_update4(L(4), R(4), hyp4, h)[0]
-        r1 = tu.tile_update4_1(L(2), h)
-        r05 = tu.tile_update5(L(3), _up1(r1))
-        disp = tu.tile_update6(L(4), _up1(r05))
+        h = tu.tile_update4(L(4), R(4), hyp4, h, trace, 4)[0]
+        disp = tu.post(L, h, trace)
         return dict(pred_disp=disp, left_feat=L(2), right_feat=R(2), left_img=left_img)
 
-    def stereo_matching(self, left_img, right_img, img_metas=None, state=None):
-        """reference hitnet.py:75-100 (eval branch) -> dict(pred_disp, left_feat, right_feat, left_img)."""
+    def stereo_matching(self, left_img, right_img, img_metas=None, state=None, trace=None):
+        """reference hitnet.py:75-100 (eval branch) -> dict(pred_disp, left_feat, right_feat, left_img).
+
+        ``trace``: None (the product: no launch, sync or allocation on its account, the launch sequence unchanged), or a
+        list that receives every stage's results as CLONES (tests/test_gpu_stereo_net_fp64.py; never passed by
+        FrameRunner or under graph capture), under both schedules.  One dict(stage, level, tensors...) per stage, in
+        the order the host issued them (which depends on the schedule: address the entries by stage and level):
+        "enc" 0..3 (enc: the U-Net's encoder skips x0..x3) and "fea" 0..4 (fea: the [2B,C,H,W] left | right batch);
+        "init" 0..4 (TileInitialization.init_level); "update" 0..4 (TileUpdate0 / TileUpdate); "r1", "up_r1", "r05",
+        "up_r05", "pred_disp" (out).  Each clone is made on the stream its stage ran on; every side stream is joined
+        into the caller's stream before this returns, so the clones are complete for whatever follows on it."""
         B = left_img.shape[0]
         if (STEREO_PIPE and not ops.Fork.serial and getattr(self, "fork_streams", True) and isinstance(self.backbone, HITUNet) and
                 isinstance(self.tile_init, TileInitialization) and isinstance(self.tile_update, TilePropagation)):
             with ops.stage("stereo"):
-                return self._stereo_matching_pipelined(left_img, right_img)
+                return self._stereo_matching_pipelined(left_img, right_img, trace)
         with ops.stage("stereo"):  # exact-fp32 convs: the disparity itself flows through these layers (ops.stage)
-            pyr = self.extract_feat(ops.batch_pair(left_img, right_img))
+            pyr = self.backbone(ops.batch_pair(left_img, right_img), trace) if trace is not None else \
+                self.extract_feat(ops.batch_pair(left_img, right_img))
             fea_l = [p[:B] for p in pyr]
             fea_r = [p[B:] for p in pyr]
             self.tile_init.fork_streams = getattr(self, "fork_streams", True)
-            _, init = self.tile_init(fea_l, fea_r)
-            disp = self.tile_update(fea_l, fea_r, init)
+            _, init = self.tile_init(fea_l, fea_r) if trace is None else self.tile_init(fea_l, fea_r, trace)
+            disp = self.tile_update(fea_l, fea_r, init) if trace is None else self.tile_update(fea_l, fea_r, init, trace)
         return dict(pred_disp=disp, left_feat=fea_l[2], right_feat=fea_r[2], left_img=left_img)
