@@ -1,11 +1,11 @@
 // Convolution family: implicit GEMM on v_mfma_f32_16x16x4_f32 (exact fp32, k-ordered fma chain).
 //
-// GEMM view:  D[co, pixel] = sum_k W[co, k] * X[k, pixel],  k = (tap, ci).
-//   MFMA A operand (16 x 4)  = weights   : lane l holds W[co = l&15][ci = c4 + (l>>4)]
-//   MFMA B operand (4 x 16)  = im2col    : lane l holds X[ci = c4 + (l>>4)][pixel = l&15]
-//   MFMA D (16 x 16)         : lane l holds D[co = 4*(l>>4) + r][pixel = l&15], r = 0..3
-// so the 16 lanes l&15 address 16 consecutive output pixels of one row: loads and stores are
-// 64-byte contiguous per channel in NCHW.
+// GEMM view:  D[pixel, co] = sum_k X[pixel, k] * W[k, co],  k = (tap, ci).
+//   MFMA A operand (16 x 4)  = im2col    : lane l holds X[pixel = l&15][ci = c4 + (l>>4)]
+//   MFMA B operand (4 x 16)  = weights   : lane l holds W[ci = c4 + (l>>4)][co = l&15]
+//   MFMA D (16 x 16)         : lane l holds D[pixel = 4*(l>>4) + r][co = l&15], r = 0..3
+// so a lane holds four consecutive output pixels of one channel: the epilogue's loads and stores are 16 bytes per
+// lane and 64 bytes contiguous per channel in NCHW (conv_kernel.h).
 //
 // Workgroup = 4 waves.  Output tile = TH x TW pixels, every wave owns NPB 16-pixel blocks and
 // all MB 16-channel blocks of the workgroup's channel group.  The input halo tile of CK
@@ -201,6 +201,8 @@ static int conv_fill(const codd_conv_params* pp, ConvK& k, size_t& lds, long lon
   const size_t hwb = (size_t)p.Hin * p.Win * sizeof(float);
   k.vec_ok = (p.Win % 4 == 0) && ((uintptr_t)p.in0.ptr % 16 == 0) && (hwb % 16 == 0) &&
              (p.C1 == 0 || (uintptr_t)p.in1.ptr % 16 == 0);
+  const auto al16 = [](const void* q) { return (uintptr_t)q % 16 == 0; };  // (a null operand pointer passes)
+  k.evec = p.store_mode == 0 && p.Wout % 4 == 0 && al16(p.out) && al16(p.res1.ptr) && al16(p.res2.ptr) && al16(p.post.ptr);
   lds = ((size_t)k.wchunk + (size_t)p.ck * k.chs) * sizeof(float);
   if (p.layout == 1) {  // quad layout: unpadded weights, input tile [cq][y][x][4]
     if (!(p.ck == 16 || p.ck == 32) || p.sx > 2 || !k.vec_ok) return CODD_EUNSUPPORTED;

@@ -133,10 +133,10 @@ __device__ __forceinline__ void conv_quad_body(const ConvK& k, int bid, float* s
           for (int a = 0; a < NPB; ++a)
 #pragma unroll
             for (int m = 0; m < MB; ++m) {
-              acc[a][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m].x, bv[a].x, acc[a][m], 0, 0, 0);
-              acc[a][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m].y, bv[a].y, acc[a][m], 0, 0, 0);
-              acc[a][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m].z, bv[a].z, acc[a][m], 0, 0, 0);
-              acc[a][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m].w, bv[a].w, acc[a][m], 0, 0, 0);
+              acc[a][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[a].x, av[m].x, acc[a][m], 0, 0, 0);
+              acc[a][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[a].y, av[m].y, acc[a][m], 0, 0, 0);
+              acc[a][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[a].z, av[m].z, acc[a][m], 0, 0, 0);
+              acc[a][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[a].w, av[m].w, acc[a][m], 0, 0, 0);
             }
         }
       }
@@ -145,7 +145,7 @@ __device__ __forceinline__ void conv_quad_body(const ConvK& k, int bid, float* s
 #undef QUAD_ISSUE
 #undef QUAD_COMMIT
 
-  conv_epilogue<NPB, MB, 4 * WREG + 16 * QREG>(k, acc, b, cog, ty, tx, wave, g, j);  // (shared with conv_mfma_kernel: conv_kernel.h)
+  conv_epilogue<NPB, MB, 4 * WREG + 16 * QREG>(k, acc, b, cog, ty, tx);  // (shared with conv_mfma_kernel: conv_kernel.h)
 }
 
 template <int NW, int NPB, int MB, int WREG, int QREG>

@@ -113,6 +113,9 @@ typedef struct codd_xs_view {
  * conv_epilogue), so nothing else is allowed: an operand whose elements overlap those of `out` at any OTHER offset (a shifted view, an
  * overlapping channel range under another coff, a different batch stride), or an input (in0 / in1 / xs) that overlaps `out`,
  * gives undefined results.  `bias` and `wpacked` never alias `out`.
+ * Alignment: res1, res2, post and out need no alignment beyond 4 bytes; where `out` and every operand present are 16-byte
+ * aligned and Wout % 4 == 0, the exact-fp32 kernels (layouts 0 and 1) take their vector path: one 16-byte access per
+ * operand and per store for four consecutive pixels of a channel -- the same bits as the 4-byte path.
  * --------------------------------------------------------------------------------------------- */
 typedef struct {
   codd_view in0, in1;

@@ -10,7 +10,10 @@
     python tools/conv_epilogue_share.py table parent=<json> noepi=<json> new=<json>
         per kernel class (kind, layout, nw, npb, mb): us per frame of each build; the epilogue's share of the first
         build is (first - noepi) / first.  ``noepi`` is a build with CODD_EXTRA_FLAGS=-DCONV_NO_EPILOGUE (conv_kernel.h):
-        it computes nothing usable and is only ever run by this replay, never through the network."""
+        it computes nothing usable and is only ever run by this replay, never through the network.  With a second run of
+        the first build as ``parent2`` the classes that ``new`` made slower by more than |parent - parent2| are listed.
+    python tools/conv_epilogue_share.py layers parent=<json> parent2=<json> noepi=<json> new=<json>
+        the same per distinct launch (us per launch), with the launches ``new`` made slower by more than the spread."""
 import collections
 import ctypes as C
 import json
@@ -173,6 +176,29 @@ def table(named):
             tot[t] += c.get(t, 0.0)
     print("%-34s %7s %8s " % ("total", "", "") + " ".join("%10.1f" % tot[t] for t in tags) +
           ("  %5.1f %%" % (100 * (tot[tags[0]] - tot["noepi"]) / tot[tags[0]]) if "noepi" in tot else ""))
+    if "parent2" in tags and "new" in tags:
+        slow = ["%s l%d nw%d npb%d mb%d (%+.1f us, spread %.1f)" % (k + (c["new"] - (c[tags[0]] + c["parent2"]) / 2, abs(c[tags[0]] - c["parent2"])))
+                for k, c in cls.items() if c["new"] - max(c[tags[0]], c["parent2"]) > abs(c[tags[0]] - c["parent2"])]
+        print("classes slower in new by more than the spread of the two parent runs: " + ("; ".join(slow) or "none"))
+
+
+def layers(named):
+    data = collections.OrderedDict((kv.split("=")[0], json.load(open(kv.split("=")[1]))["rows"]) for kv in named)
+    tags = list(data)
+    first = data[tags[0]]
+    assert all(len(rows) == len(first) for rows in data.values())
+    print("%-7s %-22s %-30s %-8s %3s %3s " % ("kind", "class", "layer", "operands", "act", "n") + " ".join("%8s" % t for t in tags) + "   share")
+    slow = []
+    for i, r in enumerate(first):
+        us = {t: data[t][i]["us"] for t in tags}
+        assert all(data[t][i]["layer"] == r["layer"] for t in tags)
+        share = "%5.1f%%" % (100 * (us[tags[0]] - us["noepi"]) / us[tags[0]]) if "noepi" in us else ""
+        print("%-7s %-22s %-30s %-8s %3d %3d " % (r["kind"], "l%d nw%d npb%d mb%d ck%d" % (r["layout"], r["nw"], r["npb"], r["mb"], r["ck"]), r["layer"],
+                                                 r["operands"], r["act"], r["per_frame"]) + " ".join("%8.2f" % us[t] for t in tags) + "  " + share)
+        if "parent2" in us and "new" in us and us["new"] - max(us[tags[0]], us["parent2"]) > abs(us[tags[0]] - us["parent2"]):
+            slow.append("%s %s (%+.2f us)" % (r["kind"], r["layer"], us["new"] - (us[tags[0]] + us["parent2"]) / 2))
+    if "parent2" in tags and "new" in tags:
+        print("launches slower in new by more than the spread of the two parent runs: " + ("; ".join(slow) or "none"))
 
 
 if __name__ == "__main__":
@@ -180,5 +206,7 @@ if __name__ == "__main__":
         record(sys.argv[2])
     elif sys.argv[1] == "time":
         time_(sys.argv[2], sys.argv[3])
+    elif sys.argv[1] == "layers":
+        layers(sys.argv[2:])
     else:
         table(sys.argv[2:])
