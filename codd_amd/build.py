@@ -31,6 +31,19 @@ def needs_build():
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def compile_cmd(src, obj):
+    """The command line that compiles one translation unit (tools/kernel_isa_diff.py compiles with it too)."""
+    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", src, "-o", obj,
+           "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-Wno-unused-result", "-Wno-pass-failed",
+           # keep MFMA accumulators in VGPRs: without it hipcc (ROCm 7.2) copies all
+           # accumulators VGPR<->AGPR around EVERY k-step of the conv loop (10 VALU per MFMA)
+           "-mllvm", "-amdgpu-mfma-vgpr-form"]
+    cmd += os.environ.get("CODD_EXTRA_FLAGS", "").split()  # dev builds, e.g. -DCONV_PROFILE
+    if os.path.basename(src) in NO_SLP:
+        cmd.append("-fno-slp-vectorize")
+    return cmd
+
+
 def build(force=False, verbose=True):
     if not force and not needs_build():
         if verbose:  # (the driver's "does it build" check: say which of the two happened)
@@ -43,15 +56,7 @@ def build(force=False, verbose=True):
     for src in sources():
         obj = src[:-4] + ".o"
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), newest_hdr):
-            cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", src, "-o", obj,
-                   "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-Wno-unused-result", "-Wno-pass-failed",
-                   # keep MFMA accumulators in VGPRs: without it hipcc (ROCm 7.2) copies all
-                   # accumulators VGPR<->AGPR around EVERY k-step of the conv loop (10 VALU per MFMA)
-                   "-mllvm", "-amdgpu-mfma-vgpr-form"]
-            cmd += os.environ.get("CODD_EXTRA_FLAGS", "").split()  # dev builds, e.g. -DCONV_PROFILE
-            if os.path.basename(src) in NO_SLP:
-                cmd.append("-fno-slp-vectorize")
-            jobs.append(cmd)
+            jobs.append(compile_cmd(src, obj))
         objs.append(obj)
 
     def run(cmd):

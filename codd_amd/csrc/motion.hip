@@ -425,28 +425,29 @@ extern "C" int codd_raft_geometry(const float* T, const float* depth1, const flo
 // Dense SE3 Gauss-Newton step (reference se3_field.py:150-170):
 //   a_ij = sigmoid(-|ae_i - ae_j|^2), |.|^2 expanded as |a_i|^2 + |a_j|^2 - 2 <a_i, a_j>,
 //   H_i = sum_j a_ij J_ij^T W_j J_ij,  b_i = sum_j a_ij J_ij^T W_j r_ij  over the (2r+1)^2 window.
-// Three launches:
-//   prep   packs everything a neighbour j contributes -- ae_j/8 (32), X_j (3), target_j (3), weight_j (3),
-//          |ae_j/8|^2 -- into one 176-byte record.
-//   build  lane = pixel i of an 8x8 tile; all 64 lanes of a wave visit the same j, so the record is read with
-//          SCALAR loads (wave-uniform address -> s_load_dwordx16, SGPR pairs feed v_pk_fma_f32 directly): no LDS,
-//          no broadcast traffic.  The kernel is VALU-issue bound; its loop is written on float2 values so that the
-//          32-term dot product is 16 packed FMAs and the 49 + 13 normal-equation updates are 23 + 8 (measured on
-//          gfx950 at 4 waves/SIMD: v_fma_f32 4.2 cycles per wave instruction, v_pk_fma_f32 5.2 -- tools/ubench/
-//          valu_rate.hip; 111 VALU instructions per neighbour against 197 for the scalar form).
-//          Work decomposition: a tile's clipped neighbourhood (1600 ... 5184 neighbours at 72x120, r = 32) is a
-//          row-major list cut into G = nj / q4 equal pieces, one per workgroup, and each piece into 4, one per
+// Three launches over one scratch buffer (GnScratch below: [partials | neighbour records | geo2]):
+//   prep   (se3_gn_prep_kernel, or gn_heads_prep_kernel which also computes the three 1x1 heads) packs everything a
+//          neighbour j contributes -- ae_j/8 (32), X_j (3), target_j (3), weight_j (3), |ae_j/8|^2 -- into one
+//          176-byte record, and the per-neighbour scalars a second time, pair-interleaved, into geo2.
+//   build  (se3_gn_build_kernel) lane = pixel i of an 8x8 tile; all 64 lanes of a wave visit the same j, so the
+//          records are read with SCALAR loads (wave-uniform address -> s_load_dwordx16, SGPR pairs feed v_pk_fma_f32
+//          directly): no broadcast traffic.  The kernel is VALU-issue bound; its loop is written on float2 values
+//          (measured on gfx950 at 4 waves/SIMD: v_fma_f32 4.2 cycles per wave instruction, v_pk_fma_f32 5.2 --
+//          tools/ubench/valu_rate.hip).
+//          Work decomposition: a tile's clipped neighbourhood (gn_window: 1600 ... 5184 neighbours at 72x120, r = 32)
+//          is a row-major list cut into G = nj / q4 equal pieces, one per workgroup, and each piece into 4, one per
 //          wave: every wave of the launch carries the same number of pairs, and the ~8000 waves are dispatched
 //          dynamically over the 4096 wave slots.  The 4 waves of a workgroup add their sums through LDS (fixed
 //          order) and write ONE [27][64] partial.
-//   solve  one workgroup per tile: 14 waves add the tile's G partials in index order (deterministic), wave 0
-//          damps, solves (Cholesky, fp64) and retracts its 64 pixels.
+//   solve  (se3_gn_solve_kernel) one workgroup per tile: 14 waves add the tile's G partials in index order
+//          (deterministic), wave 0 damps, solves (Cholesky, fp64) and retracts its 64 pixels.
 // ------------------------------------------------------------------------------------------------
 #define GN_AE 32
 #define GN_JS 44  // floats per neighbour record (16-byte aligned)
+#define GN_G2 24  // floats per neighbour PAIR in geo2: [k = 0..11][parity]: X(3) target(3) weight(3) |a|^2 0 0
 #define GN_WAVES 4
 #define GN_SOLVE_WAVES 14  // 27 sums over 14 waves: <= 2 each
-// the pair builder's second record image (se3_gn_build3_kernel): [b][y][x / 2][k = 0..11][x & 1], k = X (3), target in
+// the pair builder's second record image: [b][y][x / 2][k = 0..11][x & 1], k = X (3), target in
 // normalised image coordinates ((u - cx) / fx, (v - cy) / fy) and inverse depth, weights (wx fx^2, wy fy^2, wz), |a|^2;
 // the phantom partner of the last pixel of an odd-width row is written as zeros (depth 0 = masked, finite)
 static __device__ __forceinline__ void gn_geo2_store(float* __restrict__ geo2, int b, int h, int w, int yj, int xj, V3 X,
@@ -472,10 +473,9 @@ static __device__ __forceinline__ void gn_geo2_store_a2(float* __restrict__ geo2
 __global__ void se3_gn_prep_kernel(const float* __restrict__ ae, int ae_c, const float* __restrict__ xyz,
                                    const float* __restrict__ delta, const float* __restrict__ wgt,
                                    const float* __restrict__ d1, int h, int w, float fx, float fy, float cx, float cy,
-                                   float* __restrict__ jd, int* __restrict__ cnt, int ntiles, float* __restrict__ geo2) {
+                                   float* __restrict__ jd, float* __restrict__ geo2) {
   const int N = h * w;
   const int j = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-  if (j < ntiles) cnt[b * ntiles + j] = 0;  // arrival counters of the builder launched next (ntiles <= N)
   if (j >= N) return;
   const int yj = j / w, xj = j - yj * w;
   const float* aeb = ae + (size_t)b * ae_c * N;
@@ -524,12 +524,10 @@ __global__ __launch_bounds__(128) void gn_heads_prep_kernel(const codd_xs_view h
                                                           const float* __restrict__ xyz, const float* __restrict__ d1,
                                                           int h, int w, float fx, float fy, float cx, float cy,
                                                           float* __restrict__ jd, float* __restrict__ wout,
-                                                          int* __restrict__ cnt, int ntiles, float* __restrict__ geo2) {
+                                                          float* __restrict__ geo2) {
   const int N = h * w;
   const int lane = threadIdx.x & 63, px = lane & 15, g = lane >> 4, b = blockIdx.y;
   const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (threadIdx.x == 0)  // arrival counters of the builder launched next
-    for (int i = blockIdx.x; i < ntiles; i += gridDim.x) cnt[b * ntiles + i] = 0;
   const int n = blockIdx.x * 16 + px;
   const bool ok = n < N;
   const int j = ok ? n : N - 1;
@@ -650,33 +648,54 @@ static __host__ __device__ __forceinline__ int gn_groups(int nj, int q4, int gma
   const int g = (nj + q4 / 2) / q4;
   return g < 1 ? 1 : (g > gmax ? gmax : g);
 }
+// One axis of the neighbourhood of the 8x8 tile that starts at t0, clipped to the map: rows (columns) lo ... hi.  A tile's
+// window is two spans, nj = wy.n() * wx.n() neighbours.  (Per axis on purpose: a helper that holds both axes is optimised
+// on its own before it is inlined and changes the kernels' instruction streams.)
+struct GnSpan {
+  int lo, hi;
+  __host__ __device__ int n() const { return hi - lo + 1; }
+};
+static __host__ __device__ __forceinline__ GnSpan gn_span(int t0, int size, int radius) {
+  return GnSpan{max(t0 - radius, 0), min(t0 + 7 + radius, size - 1)};
+}
 
 // ------------------------------------------------------------------------------------------------
-// ------------------------------------------------------------------------------------------------
-// Pair builder (round 4): TWO neighbours per loop step, every operation of the geometry a packed fp32 instruction over
+// Pair builder: TWO neighbours per loop step, every operation of the geometry a packed fp32 instruction over
 // the pair (v_pk_fma / v_pk_mul / v_pk_add_f32: lane half = neighbour parity), and the normal equations in the factored
 // form of the Jacobian (reference se3_field.py:115-147; lietorch's left perturbation):
 //     J = A [I | -[Y]x],  A = d(u, v, 1/z)/dY = d * A^,  A^ = [fx 0 -fx xn; 0 fy -fy yn; 0 0 -d],  Y = (xn, yn, 1) / d
 //     S^ = a A^T W A^  (5 non-zeros: S00 S11 S02 S12 S22),   g^ = a A^T W r   (fx, fy, cx, cy folded into the records)
 //     H_tt = d^2 S^,   H_tr = d N,   H_rr = Q^T N,   N = S^ Q,   Q = -[(xn, yn, 1)]x;   b_t = d g^,   b_r = Q^T g^
-// i.e. 80 packed instructions per PAIR for the geometry where the J-entry form above issues 76 (31 of them packed) per
-// NEIGHBOUR.  The pair's per-neighbour scalars (X, target, weights, |a|^2) come from a second record image
-// ``geo2`` [b][y][x / 2][12][2] (both prep kernels write it) so that every packed source is an aligned SGPR pair; the
-// embeddings stay in the 176-byte records.  Sums are kept per parity (2 x 26 accumulators) and added at the end.
+// i.e. 80 packed instructions per PAIR for the geometry where the J-entry form (one neighbour per step, pruned: DESIGN
+// finding 60) issued 76 (31 of them packed) per NEIGHBOUR.  The pair's per-neighbour scalars (X, target, weights,
+// |a|^2) come from a second record image ``geo2`` [b][y][x / 2][12][2] (both prep kernels write it) so that every packed
+// source is an aligned SGPR pair; the embeddings stay in the 176-byte records.  Sums are kept per parity (2 x 26
+// accumulators) and added at the end.
+// AILDS = where the pixel's own embedding lives across the loop:
+//   false  in 32 registers (157 VGPRs, 3 waves per SIMD): CODD_OPT_GN_BUILDER = 3, kept as the bit-identity reference of
+//   true   in LDS ([quad q][lane] float4: conflict-free 16-byte reads; 125 VGPRs): CODD_OPT_GN_BUILDER = 5, shipped.  The
+//          same instructions on the same values in the same order -- same bits -- but four waves fit a SIMD (the
+//          scalar-load waits are 37 % of a wave's life: finding 57) at 8 KB of LDS per workgroup, which leaves the
+//          co-scheduled z|r convolution its own; the partial-sum image of the reduction aliases the embedding (the loop
+//          is over by then).
+// The kernel itself is the template: a shared __forceinline__ body under two __global__ wrappers costs SGPR spills
+// (18 -> 19, 32 -> 34) and four instructions in the pair loop; tools/kernel_isa_diff.py compares instruction streams.
 // ------------------------------------------------------------------------------------------------
-#define GN_G2 24  // floats per neighbour PAIR in geo2: [k = 0..11][parity]: X(3) target(3) weight(3) |a|^2 0 0
-__global__ __launch_bounds__(64 * GN_WAVES) void se3_gn_build3_kernel(
-    const float* __restrict__ T, const float* __restrict__ jd, const float* __restrict__ geo2, int h, int w, float fx,
-    float fy, float cx, float cy, int radius, int tiles_x, int ntiles, int q4, int gmax, float* __restrict__ part) {
-  __shared__ float red[27][64];
+#define GN_BUILD_PARAMS                                                                                                \
+  const float* __restrict__ T, const float* __restrict__ jd, const float* __restrict__ geo2, int h, int w, float fx,   \
+      float fy, float cx, float cy, int radius, int tiles_x, int ntiles, int q4, int gmax, float* __restrict__ part
+template <bool AILDS>
+__global__ __launch_bounds__(64 * GN_WAVES) void se3_gn_build_kernel(GN_BUILD_PARAMS) {
+  __shared__ __attribute__((aligned(16))) float lds[AILDS ? 8 * 64 * 4 : 27 * 64];
+  float4 (*aild)[64] = (float4 (*)[64])lds;  // [8][64] float4 (AILDS)
+  float (*red)[64] = (float (*)[64])lds;     // [27][64] floats (6.9 KB)
   const int N = h * w, wp2 = (w + 1) >> 1;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int tile = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
   const int tx0 = (tile % tiles_x) * 8, ty0 = (tile / tiles_x) * 8;
-  const int ylo = max(ty0 - radius, 0), yhi = min(ty0 + 7 + radius, h - 1);
-  const int xlo = max(tx0 - radius, 0), xhi = min(tx0 + 7 + radius, w - 1);
-  const int ncols = xhi - xlo + 1, nj = (yhi - ylo + 1) * ncols;
+  const GnSpan wy = gn_span(ty0, h, radius), wx = gn_span(tx0, w, radius);
+  const int ylo = wy.lo, xlo = wx.lo, xhi = wx.hi, ncols = wx.n(), nj = wy.n() * ncols;
   const int G = gn_groups(nj, q4, gmax);
   if (g >= G) return;
   const int slot = g * GN_WAVES + wave, nslots = G * GN_WAVES;
@@ -694,8 +713,13 @@ __global__ __launch_bounds__(64 * GN_WAVES) void se3_gn_build3_kernel(
   const SE3T Ti = se3_load(T + ((size_t)b * N + i) * 7);
   const V3 c0 = qrot(Ti.q, V3{1.f, 0.f, 0.f}), c1 = qrot(Ti.q, V3{0.f, 1.f, 0.f}), c2 = qrot(Ti.q, V3{0.f, 0.f, 1.f});
   v2f ai[GN_AE / 2];
+  if constexpr (AILDS) {
+    for (int q = wave; q < 8; q += GN_WAVES) aild[q][lane] = *(const float4*)(aip + 4 * q);  // (every wave of the tile: same pixels)
+    __syncthreads();
+  } else {
 #pragma unroll
-  for (int c = 0; c < GN_AE / 2; ++c) ai[c] = *(const v2f*)(aip + 2 * c);
+    for (int c = 0; c < GN_AE / 2; ++c) ai[c] = *(const v2f*)(aip + 2 * c);
+  }
   const float ai2 = aip[41];
   const v2f Z = {0.f, 0.f};
   v2f H00 = Z, H11 = Z, H02 = Z, H12 = Z, H22 = Z, H03 = Z, H04 = Z, H05 = Z, H13 = Z, H14 = Z, H15 = Z, H23 = Z, H24 = Z,
@@ -733,12 +757,27 @@ __global__ __launch_bounds__(64 * GN_WAVES) void se3_gn_build3_kernel(
       const bool in0 = rowin & own0 & ((unsigned)(x0 - xim) <= twor) & (Xz.x >= MIN_DEPTH) & (Yz.x >= MIN_DEPTH);
       const bool in1 = rowin & own1 & ((unsigned)(x1 - xim) <= twor) & (Xz.y >= MIN_DEPTH) & (Yz.y >= MIN_DEPTH);
       v2f p0 = Z, p1 = Z, q0 = Z, q1 = Z;
+      if constexpr (AILDS) {
+        float4 a4 = aild[0][lane], a5 = aild[1][lane];  // two quads in flight, the next one requested before this one is used
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        p0 = GN_PK(ai[2 * q], (v2f){r0[q].x, r0[q].y}, p0);
-        p1 = GN_PK(ai[2 * q + 1], (v2f){r0[q].z, r0[q].w}, p1);
-        q0 = GN_PK(ai[2 * q], (v2f){r1[q].x, r1[q].y}, q0);
-        q1 = GN_PK(ai[2 * q + 1], (v2f){r1[q].z, r1[q].w}, q1);
+        for (int q = 0; q < 8; ++q) {
+          const float4 nx = aild[q + 2 < 8 ? q + 2 : 7][lane];
+          const v2f alo = {a4.x, a4.y}, ahi = {a4.z, a4.w};
+          p0 = GN_PK(alo, (v2f){r0[q].x, r0[q].y}, p0);
+          p1 = GN_PK(ahi, (v2f){r0[q].z, r0[q].w}, p1);
+          q0 = GN_PK(alo, (v2f){r1[q].x, r1[q].y}, q0);
+          q1 = GN_PK(ahi, (v2f){r1[q].z, r1[q].w}, q1);
+          __builtin_amdgcn_sched_barrier(0);  // (keeps the compiler from hoisting all eight reads: 32 registers again)
+          a4 = a5; a5 = nx;
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          p0 = GN_PK(ai[2 * q], (v2f){r0[q].x, r0[q].y}, p0);
+          p1 = GN_PK(ai[2 * q + 1], (v2f){r0[q].z, r0[q].w}, p1);
+          q0 = GN_PK(ai[2 * q], (v2f){r1[q].x, r1[q].y}, q0);
+          q1 = GN_PK(ai[2 * q + 1], (v2f){r1[q].z, r1[q].w}, q1);
+        }
       }
       p0 += p1;
       q0 += q1;
@@ -781,6 +820,7 @@ __global__ __launch_bounds__(64 * GN_WAVES) void se3_gn_build3_kernel(
                         S2(b0), S2(b1), S2(b2), S2(b3), S2(b4), S2(b5)};
 #undef S2
   float* pp = part + (((size_t)b * ntiles + tile) * gmax + g) * 27 * 64 + lane;
+  if constexpr (AILDS) __syncthreads();  // every wave is done with the embedding image before the reduction re-uses its LDS
 #pragma unroll
   for (int w_ = 0; w_ < GN_WAVES; ++w_) {  // (one [27][64] image, waves add in index order)
     if (wave == w_) {
@@ -791,146 +831,10 @@ __global__ __launch_bounds__(64 * GN_WAVES) void se3_gn_build3_kernel(
   }
   for (int k = wave; k < 27; k += GN_WAVES) pp[k * 64] = red[k][lane];
 }
-
-// The pair builder with the pixel's own embedding in LDS (round 5, CODD_GN_AILDS=1): same instructions on the same values in
-// the same order -- same bits -- but 32 registers fewer live across the step, so that four waves fit a SIMD (the scalar-load
-// waits are 37 % of a wave's life: finding 57) without the 16 KB of affinities per workgroup that the two-pass builder costs
-// the co-scheduled z|r convolution (8 KB per workgroup here, shared with the reduction image).
-__global__ __launch_bounds__(64 * GN_WAVES) __attribute__((amdgpu_waves_per_eu(4, 4))) void se3_gn_build5_kernel(
-    const float* __restrict__ T, const float* __restrict__ jd, const float* __restrict__ geo2, int h, int w, float fx,
-    float fy, float cx, float cy, int radius, int tiles_x, int ntiles, int q4, int gmax, float* __restrict__ part) {
-  // the pixel's own embedding lives in LDS ([quad q][lane] float4: conflict-free 16-byte reads), NOT in 32 registers that
-  // are live across the whole step; the partial-sum image of the reduction aliases it (the loop is over by then)
-  __shared__ float4 aild[8][64];
-  float (*red)[64] = (float (*)[64])&aild[0][0];  // [27][64] floats = 6.9 KB of the 8 KB
-  const int N = h * w, wp2 = (w + 1) >> 1;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int tile = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
-  const int tx0 = (tile % tiles_x) * 8, ty0 = (tile / tiles_x) * 8;
-  const int ylo = max(ty0 - radius, 0), yhi = min(ty0 + 7 + radius, h - 1);
-  const int xlo = max(tx0 - radius, 0), xhi = min(tx0 + 7 + radius, w - 1);
-  const int ncols = xhi - xlo + 1, nj = (yhi - ylo + 1) * ncols;
-  const int G = gn_groups(nj, q4, gmax);
-  if (g >= G) return;
-  const int slot = g * GN_WAVES + wave, nslots = G * GN_WAVES;
-  const int s0 = (int)((long long)nj * slot / nslots), s1 = (int)((long long)nj * (slot + 1) / nslots);
-  const int ys = ylo + s0 / ncols, xs = xlo + s0 % ncols;
-  const int ye = ylo + (s1 - 1) / ncols, xe = xlo + (s1 - 1) % ncols;
-
-  const int xi = tx0 + (lane & 7), yi = ty0 + (lane >> 3);
-  const bool vi = xi < w && yi < h;
-  const int i = vi ? yi * w + xi : 0;
-  const int xim = xi - radius, yim = yi - radius;
-  const unsigned twor = 2u * (unsigned)radius;
-  const float* rec = jd + (size_t)b * N * GN_JS;
-  const float* aip = rec + (size_t)i * GN_JS;
-  const SE3T Ti = se3_load(T + ((size_t)b * N + i) * 7);
-  const V3 c0 = qrot(Ti.q, V3{1.f, 0.f, 0.f}), c1 = qrot(Ti.q, V3{0.f, 1.f, 0.f}), c2 = qrot(Ti.q, V3{0.f, 0.f, 1.f});
-  for (int q = wave; q < 8; q += GN_WAVES) aild[q][lane] = *(const float4*)(aip + 4 * q);  // (every wave of the tile: same pixels)
-  __syncthreads();
-  const float ai2 = aip[41];
-  const v2f Z = {0.f, 0.f};
-  v2f H00 = Z, H11 = Z, H02 = Z, H12 = Z, H22 = Z, H03 = Z, H04 = Z, H05 = Z, H13 = Z, H14 = Z, H15 = Z, H23 = Z, H24 = Z,
-      H25 = Z, H33 = Z, H34 = Z, H35 = Z, H44 = Z, H45 = Z, H55 = Z, b0 = Z, b1 = Z, b2 = Z, b3 = Z, b4 = Z, b5 = Z;
-#define BC(s) ((v2f){(s), (s)})
-
-  // Walk over the wave's pairs, row by row.  The records of a pair occupy 84 SGPRs (2 x 32 embedding values + 10 geometry
-  // pairs): five of the six 16-register tuples a wave has, so the compiler requests them in three or four separately
-  // awaited portions, and they cannot be requested a step ahead -- every attempt (next pair's records loaded into the
-  // registers the step has just finished with; scalar-cache warm-up loads; the embeddings through the wave's own LDS
-  // region with broadcast ds_read_b128) ended in SGPR spills through v_readlane / v_writelane, in vector loads, or at 2
-  // waves per SIMD and slower than this form (ROCm 7.2; DESIGN finding 45).
-  if (s1 > s0)
-  for (int yj = ys; yj <= ye; ++yj) {
-    const bool rowin = vi && (unsigned)(yj - yim) <= twor;
-    const float* rrow = rec + (size_t)yj * w * GN_JS;
-    const v2f* grow = (const v2f*)(geo2 + ((size_t)b * h + yj) * wp2 * GN_G2);
-    const int xa = yj == ys ? xs : xlo, xb = yj == ye ? xe : xhi;
-    for (int xp = xa >> 1; xp <= (xb >> 1); ++xp) {
-      const int x0 = 2 * xp, x1 = x0 + 1;
-      const bool own0 = x0 >= xa, own1 = x1 <= xb;  // (x0 <= xb and x1 >= xa always hold)
-      const float4* e0 = (const float4*)(rrow + (size_t)x0 * GN_JS);
-      const float4* e1 = (const float4*)(rrow + (size_t)min(x1, w - 1) * GN_JS);
-      const v2f* gp = grow + (size_t)xp * (GN_G2 / 2);
-      v2f G2[10];
-#pragma unroll
-      for (int k = 0; k < 10; ++k) G2[k] = gp[k];
-      float4 r0[8], r1[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) r0[q] = e0[q];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) r1[q] = e1[q];
-      const v2f Xx = G2[0], Xy = G2[1], Xz = G2[2];
-      const v2f Yz = GN_PK(BC(c0.z), Xx, GN_PK(BC(c1.z), Xy, GN_PK(BC(c2.z), Xz, BC(Ti.t.z))));
-      const bool in0 = rowin & own0 & ((unsigned)(x0 - xim) <= twor) & (Xz.x >= MIN_DEPTH) & (Yz.x >= MIN_DEPTH);
-      const bool in1 = rowin & own1 & ((unsigned)(x1 - xim) <= twor) & (Xz.y >= MIN_DEPTH) & (Yz.y >= MIN_DEPTH);
-      v2f p0 = Z, p1 = Z, q0 = Z, q1 = Z;
-      float4 a4 = aild[0][lane], a5 = aild[1][lane];  // two quads in flight, the next one requested before this one is used
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float4 nx = aild[q + 2 < 8 ? q + 2 : 7][lane];
-        const v2f alo = {a4.x, a4.y}, ahi = {a4.z, a4.w};
-        p0 = GN_PK(alo, (v2f){r0[q].x, r0[q].y}, p0);
-        p1 = GN_PK(ahi, (v2f){r0[q].z, r0[q].w}, p1);
-        q0 = GN_PK(alo, (v2f){r1[q].x, r1[q].y}, q0);
-        q1 = GN_PK(ahi, (v2f){r1[q].z, r1[q].w}, q1);
-        __builtin_amdgcn_sched_barrier(0);  // (keeps the compiler from hoisting all eight reads: 32 registers again)
-        a4 = a5; a5 = nx;
-      }
-      p0 += p1;
-      q0 += q1;
-      const v2f dot = {p0.x + p0.y, q0.x + q0.y};
-      const v2f e2 = GN_PK(BC(-2.f), dot, BC(ai2) + G2[9]);
-      const float ax = __builtin_amdgcn_rcpf(1.f + __expf(fmaxf(e2.x, 0.f)));
-      const float ay = __builtin_amdgcn_rcpf(1.f + __expf(fmaxf(e2.y, 0.f)));
-      const v2f a = {in0 ? ax : 0.f, in1 ? ay : 0.f};  // sigmoid(-d2), masked
-      if (__ballot(a.x > 1e-9f || a.y > 1e-9f) == 0ull) continue;  
-      const v2f Yx = GN_PK(BC(c0.x), Xx, GN_PK(BC(c1.x), Xy, GN_PK(BC(c2.x), Xz, BC(Ti.t.x))));
-      const v2f Yy = GN_PK(BC(c0.y), Xx, GN_PK(BC(c1.y), Xy, GN_PK(BC(c2.y), Xz, BC(Ti.t.y))));
-      const v2f d = {__builtin_amdgcn_rcpf(fmaxf(Yz.x, MIN_DEPTH)), __builtin_amdgcn_rcpf(fmaxf(Yz.y, MIN_DEPTH))};
-      const v2f xn = Yx * d, yn = Yy * d;
-      const v2f rx = G2[3] - xn, ry = G2[4] - yn, rz = G2[5] - d;  // (rx, ry in units of fx, fy: folded into S00, S11)
-      const v2f S00 = a * G2[6], S11 = a * G2[7], t = (a * G2[8]) * d;
-      const v2f S02 = -(S00 * xn), S12 = -(S11 * yn);
-      const v2f S22 = GN_PK(t, d, -GN_PK(S12, yn, S02 * xn));
-      const v2f g0 = S00 * rx, g1 = S11 * ry;
-      const v2f g2 = -GN_PK(t, rz, GN_PK(g1, yn, g0 * xn));
-      const v2f dd = d * d;
-      H00 = GN_PK(dd, S00, H00); H11 = GN_PK(dd, S11, H11); H02 = GN_PK(dd, S02, H02); H12 = GN_PK(dd, S12, H12);
-      H22 = GN_PK(dd, S22, H22);
-      const v2f N00 = yn * S02, N01 = GN_PK(-xn, S02, S00), N02 = -(yn * S00);
-      const v2f N10 = GN_PK(yn, S12, -S11), N11 = -(xn * S12), N12 = xn * S11;
-      const v2f N20 = GN_PK(yn, S22, -S12), N21 = GN_PK(-xn, S22, S02), N22 = GN_PK(xn, S12, -N00);
-      H03 = GN_PK(d, N00, H03); H04 = GN_PK(d, N01, H04); H05 = GN_PK(d, N02, H05);
-      H13 = GN_PK(d, N10, H13); H14 = GN_PK(d, N11, H14); H15 = GN_PK(d, N12, H15);
-      H23 = GN_PK(d, N20, H23); H24 = GN_PK(d, N21, H24); H25 = GN_PK(d, N22, H25);
-      H33 = GN_PK(yn, N20, H33) - N10; H34 = GN_PK(yn, N21, H34) - N11; H35 = GN_PK(yn, N22, H35) - N12;
-      H44 = GN_PK(-xn, N21, H44) + N01; H45 = GN_PK(-xn, N22, H45) + N02;
-      H55 = GN_PK(xn, N12, GN_PK(-yn, N02, H55));
-      b0 = GN_PK(d, g0, b0); b1 = GN_PK(d, g1, b1); b2 = GN_PK(d, g2, b2);
-      b3 = GN_PK(yn, g2, b3) - g1; b4 = GN_PK(-xn, g2, b4) + g0; b5 = GN_PK(xn, g1, GN_PK(-yn, g0, b5));
-    }
-  }
-#undef BC
-#define S2(v) ((v).x + (v).y)
-  const float Hs[27] = {S2(H00), 0.f, S2(H02), S2(H03), S2(H04), S2(H05), S2(H11), S2(H12), S2(H13), S2(H14), S2(H15),
-                        S2(H22), S2(H23), S2(H24), S2(H25), S2(H33), S2(H34), S2(H35), S2(H44), S2(H45), S2(H55),
-                        S2(b0), S2(b1), S2(b2), S2(b3), S2(b4), S2(b5)};
-#undef S2
-  float* pp = part + (((size_t)b * ntiles + tile) * gmax + g) * 27 * 64 + lane;
-  __syncthreads();  // every wave is done with the embedding image before the reduction re-uses its LDS
-#pragma unroll
-  for (int w_ = 0; w_ < GN_WAVES; ++w_) {  // (one [27][64] image, waves add in index order)
-    if (wave == w_) {
-#pragma unroll
-      for (int k = 0; k < 27; ++k) red[k][lane] = w_ == 0 ? Hs[k] : red[k][lane] + Hs[k];
-    }
-    __syncthreads();
-  }
-  for (int k = wave; k < 27; k += GN_WAVES) pp[k * 64] = red[k][lane];
-}
-
+// (amdgpu_waves_per_eu on the LDS form alone: the register form does not fit four waves)
+template __global__ void se3_gn_build_kernel<false>(GN_BUILD_PARAMS);
+template __global__ __attribute__((amdgpu_waves_per_eu(4, 4))) void se3_gn_build_kernel<true>(GN_BUILD_PARAMS);
+#undef GN_BUILD_PARAMS
 
 // Damp, solve (Cholesky, fp64) and retract the 64 pixels of one tile from its summed normal equations sums[27][64]
 // (one wave; lane = pixel).
@@ -994,7 +898,7 @@ static __device__ __forceinline__ void gn_solve_tile(float* __restrict__ T, cons
 }
 
 // One workgroup per tile: 14 waves add the tile's G partials (fixed order -> deterministic), wave 0 damps, solves
-// (Cholesky, fp64) and retracts its 64 pixels.  (The separate-launch form: CODD_GN_FUSED_SOLVE=0.)
+// (Cholesky, fp64) and retracts its 64 pixels.
 __global__ __launch_bounds__(64 * GN_SOLVE_WAVES) void se3_gn_solve_kernel(
     float* __restrict__ T, const float* __restrict__ part, int h, int w, int radius, int tiles_x, int ntiles, int q4,
     int gmax, float lm, float ep) {
@@ -1003,9 +907,8 @@ __global__ __launch_bounds__(64 * GN_SOLVE_WAVES) void se3_gn_solve_kernel(
   const int tile = blockIdx.x, b = blockIdx.y;
   const int tx0 = (tile % tiles_x) * 8, ty0 = (tile / tiles_x) * 8;
   {
-    const int ylo = max(ty0 - radius, 0), yhi = min(ty0 + 7 + radius, h - 1);
-    const int xlo = max(tx0 - radius, 0), xhi = min(tx0 + 7 + radius, w - 1);
-    const int G = gn_groups((yhi - ylo + 1) * (xhi - xlo + 1), q4, gmax);
+    const GnSpan wy = gn_span(ty0, h, radius), wx = gn_span(tx0, w, radius);
+    const int G = gn_groups(wy.n() * wx.n(), q4, gmax);
     const float* p = part + (((size_t)b * ntiles + tile) * gmax) * 27 * 64 + lane;
     for (int k = wave; k < 27; k += GN_SOLVE_WAVES) {
       float s = 0.f;
@@ -1029,46 +932,45 @@ __global__ __launch_bounds__(64 * GN_SOLVE_WAVES) void se3_gn_solve_kernel(
 // the per-workgroup partial (6.9 KB) stay in the noise.  Default 192 (a pair slot is lost at each end of a row segment:
 // 103.5 us at 128, 100.3 at 192, 99.4 at 256, 104.7 at 384); CODD_OPT_GN_Q4 selects another grouping -- another fp32
 // summation order of the same normal equations, which the parity tests use as a re-association probe.
-static inline int gn_q4() {
-  const int q = codd_opt(CODD_OPT_GN_Q4);
-  return q < 16 ? 16 : q;
-}
-static inline int gn_gmax(int radius) {
-  const int NC = 8 + 2 * radius;
-  return gn_groups(NC * NC, gn_q4(), 1 << 20);
-}
-
-// floats of scratch in front of the pair builder's geo2 image: [partials | neighbour records | per-tile counters]
-static inline size_t gn_geo2_offset(int B, int h, int w, int radius) {
-  const int ntiles = cdiv(w, 8) * cdiv(h, 8);
-  const size_t n = (size_t)B * ntiles * gn_gmax(radius) * 27 * 64 + (size_t)B * h * w * GN_JS + (size_t)B * ntiles;
-  return (n + 3) & ~(size_t)3;
+//
+// The scratch of one step, laid out in ONE place: [part: per-workgroup [27][64] partials, gmax per tile | jd: 176-byte
+// neighbour records | geo2: the pair-interleaved per-neighbour scalars].  part and jd are multiples of 4 floats, so
+// geo2 is 16-byte aligned when Hb is.  CODD_OPT_GN_Q4 is read once: sizes, pointers and launch arguments of a call agree
+// (a caller that changes the option between codd_se3_gn_scratch and the step still under-sizes Hb: ADVICE finding 2, open).
+struct GnScratch {
+  float *part, *jd, *geo2;
+  long long floats;
+  int q4, gmax;  // gmax = groups of an unclipped window: the part slots per tile
+};
+static_assert(GN_JS % 4 == 0 && (27 * 64) % 4 == 0, "geo2 must stay 16-byte aligned");
+static GnScratch gn_scratch(float* Hb, int B, int h, int w, int radius) {
+  GnScratch sc;
+  const int q = codd_opt(CODD_OPT_GN_Q4);  // the one read of the option per call
+  sc.q4 = q < 16 ? 16 : q;
+  const int full = gn_span(radius, 8 + 2 * radius, radius).n();  // (a map this large clips nothing of the tile at radius)
+  sc.gmax = gn_groups(full * full, sc.q4, 1 << 20);
+  const long long part = (long long)B * cdiv(w, 8) * cdiv(h, 8) * sc.gmax * 27 * 64, jd = (long long)B * h * w * GN_JS;
+  sc.part = Hb;
+  sc.jd = Hb ? Hb + part : nullptr;  // (Hb == nullptr: codd_se3_gn_scratch wants the size alone)
+  sc.geo2 = Hb ? Hb + part + jd : nullptr;
+  sc.floats = part + jd + (long long)B * h * ((w + 1) / 2) * GN_G2;
+  return sc;
 }
 extern "C" long long codd_se3_gn_scratch(int B, int h, int w, int radius) {
-  // (+ 2 pairs: the pair builder's warm-up loads read one pair past the step's own)
-  return (long long)gn_geo2_offset(B, h, w, radius) + ((long long)B * h * ((w + 1) / 2) + 2) * GN_G2;
-}
-static inline int* gn_counters(float* Hb, int B, int h, int w, int radius) {
-  const int ntiles = cdiv(w, 8) * cdiv(h, 8);
-  return (int*)(Hb + (size_t)B * ntiles * gn_gmax(radius) * 27 * 64 + (size_t)B * h * w * GN_JS);
+  return gn_scratch(nullptr, B, h, w, radius).floats;
 }
 
 static int gn_build_solve(float* T, int B, int h, int w, float fx, float fy, float cx, float cy, int radius, float lm,
-                          float ep, float* Hb, hipStream_t s) {
+                          float ep, const GnScratch& sc, hipStream_t s) {
   const int tiles_x = cdiv(w, 8), ntiles = tiles_x * cdiv(h, 8);
-  const int q4 = gn_q4(), gmax = gn_gmax(radius);
-  float* part = Hb;
-  const float* jd = Hb + (size_t)B * ntiles * gmax * 27 * 64;
   // CODD_OPT_GN_BUILDER: 5 (default) = the pixel's own embedding in LDS (125 VGPRs), 3 = in registers (157 VGPRs): the same
   // instructions on the same values in the same order (bit-identical; tests/test_gpu_motion_ops.py)
-  if (codd_opt(CODD_OPT_GN_BUILDER) == 3)
-    se3_gn_build3_kernel<<<dim3(ntiles, gmax, B), 64 * GN_WAVES, 0, s>>>(T, jd, Hb + gn_geo2_offset(B, h, w, radius), h, w, fx, fy,
-                                                                        cx, cy, radius, tiles_x, ntiles, q4, gmax, part);
-  else
-    se3_gn_build5_kernel<<<dim3(ntiles, gmax, B), 64 * GN_WAVES, 0, s>>>(T, jd, Hb + gn_geo2_offset(B, h, w, radius), h, w, fx, fy,
-                                                                        cx, cy, radius, tiles_x, ntiles, q4, gmax, part);
+  const auto build = codd_opt(CODD_OPT_GN_BUILDER) == 3 ? se3_gn_build_kernel<false> : se3_gn_build_kernel<true>;
+  build<<<dim3(ntiles, sc.gmax, B), 64 * GN_WAVES, 0, s>>>(T, sc.jd, sc.geo2, h, w, fx, fy, cx, cy, radius, tiles_x, ntiles,
+                                                          sc.q4, sc.gmax, sc.part);
   CODD_LAUNCH_CHECK();
-  se3_gn_solve_kernel<<<dim3(ntiles, B), 64 * GN_SOLVE_WAVES, 0, s>>>(T, part, h, w, radius, tiles_x, ntiles, q4, gmax, lm, ep);
+  se3_gn_solve_kernel<<<dim3(ntiles, B), 64 * GN_SOLVE_WAVES, 0, s>>>(T, sc.part, h, w, radius, tiles_x, ntiles, sc.q4,
+                                                                     sc.gmax, lm, ep);
   CODD_LAUNCH_CHECK();
   return CODD_OK;
 }
@@ -1078,14 +980,12 @@ extern "C" int codd_se3_gn_step(float* T, const float* ae, int ae_c, const float
                                 float cx, float cy, int radius, float lm, float ep, float* Hb, void* stream) {
   if (!T || !ae || !xyz || !delta || !weight || !depth1 || !Hb || ae_c < 1 || ae_c > GN_AE || radius < 0)
     return CODD_EINVAL;
-  const int ntiles = cdiv(w, 8) * cdiv(h, 8);
-  float* jd = Hb + (size_t)B * ntiles * gn_gmax(radius) * 27 * 64;
+  const GnScratch sc = gn_scratch(Hb, B, h, w, radius);
   hipStream_t s = (hipStream_t)stream;
   se3_gn_prep_kernel<<<dim3(cdiv(h * w, 128), B), 128, 0, s>>>(ae, ae_c, xyz, delta, weight, depth1, h, w, fx, fy, cx,
-                                                             cy, jd, gn_counters(Hb, B, h, w, radius), ntiles,
-                                                             Hb + gn_geo2_offset(B, h, w, radius));
+                                                             cy, sc.jd, sc.geo2);
   CODD_LAUNCH_CHECK();
-  return gn_build_solve(T, B, h, w, fx, fy, cx, cy, radius, lm, ep, Hb, s);
+  return gn_build_solve(T, B, h, w, fx, fy, cx, cy, radius, lm, ep, sc, s);
 }
 
 extern "C" int codd_se3_gn_step_heads(float* T, codd_xs_view hidden, const void* head_w, const float* head_b,
@@ -1095,14 +995,12 @@ extern "C" int codd_se3_gn_step_heads(float* T, codd_xs_view hidden, const void*
   if (!T || !head_w || ((uintptr_t)head_w & 15) || !head_b || !xyz || !depth1 || !weight_out || !Hb || radius < 0 ||
       !xs_view_ok(hidden, 768, h, w))
     return CODD_EINVAL;
-  const int ntiles = cdiv(w, 8) * cdiv(h, 8);
-  float* jd = Hb + (size_t)B * ntiles * gn_gmax(radius) * 27 * 64;
+  const GnScratch sc = gn_scratch(Hb, B, h, w, radius);
   hipStream_t s = (hipStream_t)stream;
   gn_heads_prep_kernel<<<dim3(cdiv(h * w, 16), B), 128, 0, s>>>(hidden, (const uint4*)head_w, head_b, xyz, depth1, h, w, fx, fy, cx, cy,
-                                                               jd, weight_out, gn_counters(Hb, B, h, w, radius), ntiles,
-                                                               Hb + gn_geo2_offset(B, h, w, radius));
+                                                               sc.jd, weight_out, sc.geo2);
   CODD_LAUNCH_CHECK();
-  return gn_build_solve(T, B, h, w, fx, fy, cx, cy, radius, lm, ep, Hb, s);
+  return gn_build_solve(T, B, h, w, fx, fy, cx, cy, radius, lm, ep, sc, s);
 }
 
 // ------------------------------------------------------------------------------------------------

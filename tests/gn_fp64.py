@@ -227,7 +227,7 @@ def gn_groups(nj, q4, gmax):
 
 
 def slot_starts(h, w, radius, q4, tile_y, tile_x):
-    """The first neighbour (y, x) of every wave slot of tile (tile_y, tile_x), as se3_gn_build{3,5}_kernel cut the
+    """The first neighbour (y, x) of every wave slot of tile (tile_y, tile_x), as se3_gn_build_kernel<false|true> cut the
     tile's clipped window: G = gn_groups(nj, q4, gmax) workgroups x 4 waves, slot s starts at nj * s // (4 G)."""
     q4 = max(q4, 16)
     gmax = gn_groups((8 + 2 * radius) ** 2, q4, 1 << 20)

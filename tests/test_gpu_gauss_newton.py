@@ -92,7 +92,8 @@ def test_gn_step_with_large_common_embedding_component():
 def test_gn_step_does_not_read_stale_scratch(case):
     """codd_se3_gn_step with its scratch filled with NaN (and a little larger than asked for) and with zeros: the same
     bits, all finite -- no partial, record or geo2 slot is read before a kernel of the step wrote it (ops.se3_gn_step
-    takes its scratch from torch.empty)."""
+    takes its scratch from torch.empty).  The floats past codd_se3_gn_scratch are still NaN afterwards: no kernel of the
+    step writes past the size the library asks for."""
     from codd_amd import _abi
     lib = _abi.load()
     c = _case(case)
@@ -114,6 +115,8 @@ def test_gn_step_does_not_read_stale_scratch(case):
                                                     torch.cuda.current_stream().cuda_stream), "se3_gn_step")
                     torch.cuda.synchronize()
                     outs.append(T.cpu())
+                    if extra:
+                        assert torch.isnan(scratch[n:]).all(), (case, builder, q4, "a write past codd_se3_gn_scratch")
             finally:
                 _defaults()
             assert torch.isfinite(outs[0]).all(), (case, builder, q4)

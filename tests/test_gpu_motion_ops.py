@@ -990,8 +990,8 @@ def _gn_two_steps(ops):
 
 
 def test_se3_gn_pair_builder_with_embedding_in_lds_is_bit_identical():
-    """se3_gn_build5_kernel (the shipped builder: the pixel's own embedding read from LDS instead of 32 registers, four waves
-    per SIMD) issues the pair builder's instructions on the same values in the same order as se3_gn_build3_kernel
+    """se3_gn_build_kernel<true> (the shipped builder: the pixel's own embedding read from LDS instead of 32 registers, four
+    waves per SIMD) issues the pair builder's instructions on the same values in the same order as se3_gn_build_kernel<false>
     (CODD_OPT_GN_BUILDER = 3, kept as its reference): torch.equal on the updated field."""
     from codd_amd import _abi, ops
     outs = []

@@ -103,7 +103,7 @@ def test_gauss_newton_builder_against_autograd_jacobians():
 
 
 def test_factored_normal_equations_of_the_pair_builder_equal_jt_w_j():
-    """se3_gn_build3_kernel (csrc/motion.hip) never forms the 3x6 Jacobian: it accumulates
+    """se3_gn_build_kernel (csrc/motion.hip) never forms the 3x6 Jacobian: it accumulates
         S^ = a A^T W A^  (A^ = [fx 0 -fx xn; 0 fy -fy yn; 0 0 -d], Y = (xn, yn, 1) / d),   N = S^ Q,   Q = -[(xn, yn, 1)]x,
         H_tt = d^2 S^,  H_tr = d N,  H_rr = Q^T N,   g^ = a A^T W r,  b_t = d g^,  b_r = Q^T g^
     with the pixel residuals taken in units of fx, fy (normalised targets, weights x f^2: the record image ``geo2``).  Here
@@ -128,7 +128,7 @@ def test_factored_normal_equations_of_the_pair_builder_equal_jt_w_j():
         Wm = torch.diag(a * w)
         H_ref, b_ref = J.t() @ Wm @ J, J.t() @ Wm @ r
 
-        # the kernel's formulas (names as in se3_gn_build3_kernel)
+        # the kernel's formulas (names as in se3_gn_build_kernel)
         Y = (Mi @ torch.cat([X, X.new_ones(1)]))[:3]
         d = 1.0 / Y[2]
         xn, yn = Y[0] * d, Y[1] * d
