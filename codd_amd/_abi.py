@@ -121,6 +121,8 @@ SIGNATURES = {
     "codd_preprocess": (_i, [_p, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _p, _p]),
     "codd_fusion_blend": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "codd_ingest_pair": (_i, [_p, _p, _i, _i, _i, c_float_p, c_float_p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
+    "codd_ingest_frames": (_i, [_p, _p, _i, _i, _i, _i, _ll, c_float_p, c_float_p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
+    "codd_frame_bytes": (_ll, [_i, _i, _i, _ll]),
     "codd_export_depth": (_i, [_p, _i, _i, _i, _i, _i, _f, _p, _p]),
     "codd_export_motion": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p]),
     "codd_ego_motion_scratch": (_ll, [_i, _i]),

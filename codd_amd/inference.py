@@ -55,7 +55,24 @@ def parse_args(argv=None):
     p.add_argument("--occ-px", type=float, default=None, help="--confidence: occlusion tolerance in pixels (default 1.0)")
     p.add_argument("--tau", type=float, default=None, help="--confidence: mismatch threshold in grey levels (default 24.0)")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
+    p.add_argument("--pixel-format", choices=list(ops.FRAME_FORMATS), default=None,
+                   help="--live: the frame files are raw byte dumps in this camera format (what `v4l2-ctl --stream-to` "
+                   "writes, one frame per file, selected by --img-suffix), decoded on the GPU; needs --frame-size")
+    p.add_argument("--frame-size", default=None, metavar="HxW", help="--pixel-format: height x width of a frame in pixels")
+    p.add_argument("--pitch", type=int, default=None, help="--pixel-format: bytes per source row (default: tight)")
+    p.add_argument("--yuv", choices=list(ops.YUV_MATRICES), default=None,
+                   help="--pixel-format yuyv / uyvy / nv12: the YUV -> RGB matrix (default bt601; bt709 for HD video range, "
+                   "jpeg for full range)")
     args = p.parse_args(argv)
+    if args.pixel_format is not None:
+        if not args.live:
+            p.error("--pixel-format needs --live")
+        m = re.fullmatch(r"(\d+)x(\d+)", args.frame_size or "")
+        if not m:
+            p.error("--pixel-format needs --frame-size HxW")
+        args.frame_size = (int(m.group(1)), int(m.group(2)))
+    elif args.frame_size is not None or args.pitch is not None or args.yuv is not None:
+        p.error("--frame-size / --pitch / --yuv need --pixel-format")
     if args.motion is not None and not args.live:
         p.error("--motion needs --live")
     if args.ego and not args.live:
@@ -115,6 +132,22 @@ def iter_frames(lefts, rights):
     from PIL import Image
     for lp, rp in zip(lefts, rights):
         yield tuple(np.ascontiguousarray(np.array(Image.open(p).convert("RGB"))) for p in (lp, rp))
+
+
+def iter_raw_frames(lefts, rights, fmt, shape, pitch=None):
+    """(left, right) uint8 [rows, pitch] pairs of raw ``fmt`` frames (live.frame_layout), each file read only when asked
+    for; a file that is not exactly one frame long is a ValueError."""
+    from .live import frame_layout
+    rows, _, p, nbytes = frame_layout(fmt, shape[0], shape[1], pitch)
+    for lp, rp in zip(lefts, rights):
+        pair = []
+        for path in (lp, rp):
+            a = np.fromfile(path, dtype=np.uint8)
+            if a.size != nbytes:
+                raise ValueError(f"{path}: {a.size} bytes, expected one {fmt} frame of {shape[0]}x{shape[1]} "
+                                 f"(pitch {p}) = {nbytes} bytes")
+            pair.append(a.reshape(rows, p))
+        yield tuple(pair)
 
 
 def live_results(session, frames, depth=2):
@@ -200,7 +233,8 @@ def run_live(args, model, videos):
     results go to <show-dir>/<name>.disp.pred.npz ([1, frames, h, w], as the default path writes) and, with --motion,
     <name>.motion.pred.npz ([1, frames, h, w, C]; a frame without a field is all NaN) and, with --ego,
     <name>.ego.pred.npz (pose, stats, camera_to_world, moving; a frame without a field is NaN, 255 in moving) and, with
-    --confidence, <name>.conf.pred.npz (flags and residual, [1, frames, h, w] each)."""
+    --confidence, <name>.conf.pred.npz (flags and residual, [1, frames, h, w] each).  With --pixel-format the frame files
+    are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU."""
     from PIL import Image
     from .live import LiveSession
     maps = None
@@ -210,9 +244,12 @@ def run_live(args, model, videos):
     extra = dict(egomotion=True) if args.ego else {}
     if args.confidence:
         extra["confidence"] = {k: v for k, v in (("occ_px", args.occ_px), ("tau", args.tau)) if v is not None} or True
+    raw = getattr(args, "pixel_format", None)
+    if raw:
+        extra.update(pixel_format=raw, pitch=args.pitch, yuv=args.yuv or "bt601")
     sessions = {}
     for name, lefts, rights in videos:
-        w, h = Image.open(lefts[0]).size
+        h, w = args.frame_size if raw else Image.open(lefts[0]).size[::-1]
         s = sessions.get((h, w))
         if s is None:
             s = sessions[(h, w)] = LiveSession(model, (h, w), intrinsics=CUSTOM["intrinsics"], calib=CUSTOM["calib"],
@@ -238,7 +275,8 @@ def run_live(args, model, videos):
                 cres = cflags.spool("residual", (1, nf, h, w), np.float32)
         n = 0
         try:
-            for res in live_results(s, iter_frames(lefts, rights)):
+            frames = iter_raw_frames(lefts, rights, raw, (h, w), args.pitch) if raw else iter_frames(lefts, rights)
+            for res in live_results(s, frames):
                 n += 1
                 if args.confidence:
                     res, c = res[:-1] if (args.motion or args.ego) else res[0], res[-1]

@@ -25,6 +25,11 @@ With ``confidence=`` the session says which depth pixels to trust: ``codd_export
 ``codd_export_depth`` on the frame's disparity and on the two normalised images the frame graph read -- the buffers the
 ``fill`` closure below was handed for this frame, which the graph only reads -- and returns per-pixel flags (out of view,
 occluded in the right image, photometric mismatch, invalid) and the photometric residual.  It needs no motion stage.
+
+With ``pixel_format=`` the session takes frames as a camera hands them out -- mono8, YUYV / UYVY, NV12 or a Bayer mosaic,
+with a row pitch -- uploads those bytes (1 to 2 per pixel instead of 3) and decodes them inside the ingest launch:
+``codd_ingest_frames`` stands where ``codd_ingest_pair`` stands above and writes the bits ``codd_ingest_pair`` writes on
+the decoded RGB images, so that everything behind it is unchanged.
 """
 from collections import deque, namedtuple
 
@@ -36,6 +41,8 @@ from .runtime import FrameRunner
 
 OUTPUTS = ("disp", "depth", "disp_u16")
 MOTIONS = ("flow2d", "flow_dd", "sceneflow")
+PIXEL_FORMATS = ("rgb8",) + tuple(ops.FRAME_FORMATS)  # rgb8: packed [h,w,3] through codd_ingest_pair; the others raw
+YUVS = tuple(ops.YUV_MATRICES)
 DEPTH = 2  # frames in flight: input, device and host output slots are double-buffered
 EGO_DEFAULTS = dict(iters=5, delta_px=1.0, tau_px=2.0, min_valid=16)
 CONF_DEFAULTS = dict(occ_px=1.0, tau=24.0)
@@ -147,6 +154,57 @@ def check_frame(a, shape, name="frame"):
     return a
 
 
+def frame_layout(fmt, h, w, pitch=None):
+    """``(rows, row_bytes, pitch, nbytes)`` of one view of an h x w frame in pixel format ``fmt``: a host frame is
+    ``rows x pitch`` bytes, of which the first ``row_bytes`` of a row carry pixels (nv12: ``rows`` = 3h/2, the Y plane
+    and the interleaved U V plane behind it).  ``pitch`` None is tight.  ValueError for an unknown format, a violated
+    size rule (yuyv / uyvy: w even; nv12: w and h even; Bayer: h, w >= 2) or a pitch below ``row_bytes``; ``rgb8`` is
+    tight only.  The same rules as codd_frame_bytes, restated here so that no library is needed to validate."""
+    if fmt not in PIXEL_FORMATS:
+        raise ValueError(f"pixel_format: one of {PIXEL_FORMATS} expected, got {fmt!r}")
+    h, w = int(h), int(w)
+    if h <= 0 or w <= 0:
+        raise ValueError(f"shape: positive (h, w) expected, got {(h, w)}")
+    if fmt in ("yuyv", "uyvy", "nv12") and w % 2:
+        raise ValueError(f"{fmt}: an even width is expected, got {w}")
+    if fmt == "nv12" and h % 2:
+        raise ValueError(f"nv12: an even height is expected, got {h}")
+    if fmt.startswith("bayer_") and (h < 2 or w < 2):
+        raise ValueError(f"{fmt}: at least 2 x 2 pixels are expected, got {h} x {w}")
+    row_bytes = w * {"rgb8": 3, "yuyv": 2, "uyvy": 2}.get(fmt, 1)
+    if fmt == "rgb8" and pitch is not None:
+        raise ValueError("pitch: not supported for rgb8 (packed 3-byte frames are tight)")
+    p = row_bytes if pitch is None else int(pitch)
+    if p < row_bytes:
+        raise ValueError(f"pitch: at least the row's {row_bytes} bytes expected for {fmt} of width {w}, got {pitch}")
+    rows = h + h // 2 if fmt == "nv12" else h
+    return rows, row_bytes, p, rows * p
+
+
+def check_raw_frame(a, fmt, shape, pitch=None, name="frame"):
+    """A C-contiguous uint8 numpy array or CPU tensor holding one raw ``fmt`` frame: shape ``(rows, pitch)`` of
+    ``frame_layout`` or, for tight yuyv / uyvy, ``(h, w, 2)``; else TypeError / ValueError (no device call)."""
+    rows, _, p, _ = frame_layout(fmt, shape[0], shape[1], pitch)
+    if isinstance(a, torch.Tensor):
+        if a.is_cuda:
+            raise TypeError(f"{name}: a host (CPU) tensor is expected, got one on {a.device}")
+        dtype_ok, contiguous, shp = a.dtype == torch.uint8, a.is_contiguous(), tuple(a.shape)
+    elif isinstance(a, np.ndarray):
+        dtype_ok, contiguous, shp = a.dtype == np.uint8, a.flags["C_CONTIGUOUS"], tuple(a.shape)
+    else:
+        raise TypeError(f"{name}: numpy array or CPU tensor expected, got {type(a).__name__}")
+    if not dtype_ok:
+        raise ValueError(f"{name}: dtype uint8 expected, got {a.dtype}")
+    accepted = [(rows, p)]
+    if fmt in ("yuyv", "uyvy") and p == 2 * shape[1]:
+        accepted.append((shape[0], shape[1], 2))
+    if shp not in accepted:
+        raise ValueError(f"{name}: {fmt} frame of shape {' or '.join(map(str, accepted))} expected, got {shp}")
+    if not contiguous:
+        raise ValueError(f"{name}: a C-contiguous array is expected")
+    return a
+
+
 def _check_maps(rectify, shape):
     if rectify is None:
         return None
@@ -192,10 +250,18 @@ class LiveSession:
     ``confidence`` (False, True, or a dict overriding ``occ_px`` (1.0 pixel) and ``tau`` (24.0 grey levels)): ``pop`` and
     ``step`` also return a ``Confidence(flags, residual)`` on the CURRENT frame's grid, for every frame (never None).  It
     needs no motion stage.
+
+    ``pixel_format`` (one of ``PIXEL_FORMATS``; "rgb8", the default, is the packed [h,w,3] frame above, with ``bgr``):
+    with a raw format a frame is a C-contiguous uint8 array or CPU tensor of ``rows x pitch`` bytes (``frame_layout``):
+    mono8 and Bayer ``(h, pitch)``; yuyv / uyvy ``(h, pitch)`` or, when tight, ``(h, w, 2)``; nv12 ``(3h/2, pitch)``, the
+    Y plane and the interleaved U V plane behind it.  ``pitch`` (bytes per row, None: tight) and ``yuv`` ("bt601" and
+    "bt709" video range, "jpeg" full range) describe the source; ``bgr`` and ``pitch`` do not combine with the other
+    family of formats (ValueError).  The decode is defined in include/codd_hip.h (codd_ingest_frames).
     """
 
     def __init__(self, estimator, shape, intrinsics=(1050.0, 1050.0, 480.0, 270.0), calib=210.0, output="depth",
-                 bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False):
+                 bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False,
+                 pixel_format="rgb8", yuv="bt601", pitch=None):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
@@ -209,6 +275,12 @@ class LiveSession:
         h, w = int(shape[0]), int(shape[1])
         if h <= 0 or w <= 0:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
+        if yuv not in YUVS:
+            raise ValueError(f"yuv: one of {YUVS} expected, got {yuv!r}")
+        self._layout = frame_layout(pixel_format, h, w, pitch)  # (rows, row_bytes, pitch, nbytes); ValueError if invalid
+        if pixel_format != "rgb8" and bgr:
+            raise ValueError(f"bgr=True is for rgb8 frames only (pixel_format={pixel_format!r} names its own byte order)")
+        self.pixel_format, self.yuv, self.pitch = pixel_format, yuv, None if pitch is None else int(pitch)
         self.est, self.shape, self.output, self.bgr, self.calib = estimator, (h, w), output, bool(bgr), float(calib)
         self.padded = (-(-h // divisor) * divisor, -(-w // divisor) * divisor)
         self._maps_host = _check_maps(rectify, (h, w))
@@ -238,8 +310,10 @@ class LiveSession:
         self.dev = dev
         odt = torch.int16 if self.output == "disp_u16" else torch.float32  # (uint16 bits; handed out as numpy uint16)
         with torch.cuda.device(dev):
-            self._h_in = [[torch.empty(h, w, 3, dtype=torch.uint8, pin_memory=True) for _ in range(2)] for _ in range(DEPTH)]
-            self._d_in = [[torch.empty(h, w, 3, dtype=torch.uint8, device=dev) for _ in range(2)] for _ in range(DEPTH)]
+            # rgb8: [h,w,3]; a raw format: the frame's bytes, flat (frame_layout: rows x pitch)
+            slot = (h, w, 3) if self.pixel_format == "rgb8" else (self._layout[3],)
+            self._h_in = [[torch.empty(slot, dtype=torch.uint8, pin_memory=True) for _ in range(2)] for _ in range(DEPTH)]
+            self._d_in = [[torch.empty(slot, dtype=torch.uint8, device=dev) for _ in range(2)] for _ in range(DEPTH)]
             self._scratch = tuple(torch.empty(1, 3, H, W, dtype=torch.float32, device=dev) for _ in range(2))
             self._maps = None
             if self._maps_host is not None:
@@ -276,8 +350,12 @@ class LiveSession:
     # ---- pipeline -----------------------------------------------------------------------------------
     def push(self, left_u8, right_u8):
         """Enqueue one frame.  Returns once both images sit in the session's pinned slot."""
-        check_frame(left_u8, self.shape, "left")
-        check_frame(right_u8, self.shape, "right")
+        raw = self.pixel_format != "rgb8"
+        for a, name in ((left_u8, "left"), (right_u8, "right")):
+            if raw:
+                check_raw_frame(a, self.pixel_format, self.shape, self.pitch, name)
+            else:
+                check_frame(a, self.shape, name)
         if not self._open_done:
             self._open()
         if len(self._inflight) == DEPTH:
@@ -293,6 +371,8 @@ class LiveSession:
                     self._s_up.wait_event(self._e_ingest[k])  # the slot's previous frame has been read by its ingest
                 # view by view: the left image's upload runs while the host copies the right one into its slot
                 for dev_slot, host_slot, src in zip(self._d_in[k], self._h_in[k], (left_u8, right_u8)):
+                    if raw:
+                        src = src.reshape(-1)  # (C-contiguous: a view)
                     if isinstance(src, torch.Tensor):
                         host_slot.copy_(src)
                     else:
@@ -305,7 +385,11 @@ class LiveSession:
 
             def fill(left, right):
                 images[:] = (left, right)  # (the frame's normalised images: read again by export_confidence)
-                ops.ingest_pair(self._d_in[k][0], self._d_in[k][1], left, right, bgr=self.bgr, maps=self._maps)
+                if raw:
+                    ops.ingest_frames(self._d_in[k][0], self._d_in[k][1], left, right, self.pixel_format, self.shape,
+                                      yuv=self.yuv, pitch=self.pitch, maps=self._maps)
+                else:
+                    ops.ingest_pair(self._d_in[k][0], self._d_in[k][1], left, right, bgr=self.bgr, maps=self._maps)
                 self._e_ingest[k].record(compute)
 
             disp = self.runner.step_fill(fill, self._scratch)

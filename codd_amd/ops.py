@@ -1750,6 +1750,51 @@ def ingest_pair(left_u8, right_u8, out_left, out_right, bgr=True, maps=None, mea
                                     out_left.data_ptr(), out_right.data_ptr(), _stream()), "ingest_pair")
 
 
+FRAME_FORMATS = dict(mono8=1, yuyv=2, uyvy=3, nv12=4, bayer_rggb=5, bayer_grbg=6, bayer_gbrg=7,
+                     bayer_bggr=8)  # CODD_FMT_* of include/codd_hip.h
+YUV_MATRICES = dict(bt601=0, bt709=1, jpeg=2)  # CODD_YUV_*
+
+
+def frame_bytes(fmt, h, w, pitch=None):
+    """Bytes of one view of a raw ``fmt`` frame (codd_frame_bytes); ValueError for an invalid combination."""
+    if fmt not in FRAME_FORMATS:
+        raise ValueError(f"pixel format: one of {tuple(FRAME_FORMATS)} expected, got {fmt!r}")
+    n = _abi.load().codd_frame_bytes(FRAME_FORMATS[fmt], int(h), int(w), int(pitch or 0))
+    if n < 0:
+        raise ValueError(f"{fmt}: invalid size {h}x{w} or pitch {pitch} (see codd_ingest_frames in include/codd_hip.h)")
+    return n
+
+
+def ingest_frames(left_u8, right_u8, out_left, out_right, fmt, shape, yuv="bt601", pitch=None, maps=None,
+                  mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """``ingest_pair`` on raw camera frames: both views, flat or shaped uint8 device tensors of exactly
+    ``frame_bytes(fmt, h, w, pitch)`` in format ``fmt`` (a key of FRAME_FORMATS), are decoded to RGB inside the launch
+    (never in memory) and written normalised, rectified and reflect-padded into the caller's [..,3,H,W] buffers --
+    the bits ``ingest_pair`` gives on the decoded images.  ``shape``: (h, w); ``yuv``: a key of YUV_MATRICES (ignored
+    for mono and Bayer); ``pitch``: bytes per source row, None = tight; ``maps`` as ``ingest_pair``."""
+    lib = _abi.load()
+    _require_gpu(left_u8)
+    h, w = int(shape[0]), int(shape[1])
+    nbytes = frame_bytes(fmt, h, w, pitch)
+    if yuv not in YUV_MATRICES:
+        raise ValueError(f"yuv: one of {tuple(YUV_MATRICES)} expected, got {yuv!r}")
+    for t in (left_u8, right_u8):
+        assert t.dtype == torch.uint8 and t.numel() == nbytes and t.is_contiguous() and t.is_cuda
+    H, W = out_left.shape[-2:]
+    for t in (out_left, out_right):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and t.numel() == 3 * H * W
+    ptrs = []
+    for pair in (maps or (None, None)):
+        for m in (pair or (None, None)):
+            if m is not None:
+                assert m.dtype == torch.float32 and tuple(m.shape) == (h, w) and m.is_contiguous() and m.is_cuda
+            ptrs.append(None if m is None else m.data_ptr())
+    m, s = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    _abi.check(lib.codd_ingest_frames(left_u8.data_ptr(), right_u8.data_ptr(), FRAME_FORMATS[fmt], YUV_MATRICES[yuv], h, w,
+                                      int(pitch or 0), m, s, *ptrs, H, W, out_left.data_ptr(), out_right.data_ptr(),
+                                      _stream()), "ingest_frames")
+
+
 EXPORT_MODES = dict(disp=0, depth=1, disp_u16=2)  # CODD_EXPORT_* of include/codd_hip.h
 
 

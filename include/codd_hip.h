@@ -561,6 +561,63 @@ int codd_ingest_pair(const unsigned char* left, const unsigned char* right, int 
                      const float* stdv, const float* lmap_x, const float* lmap_y, const float* rmap_x,
                      const float* rmap_y, int H, int W, float* out_left, float* out_right, void* stream);
 
+/* Live-session ingest of raw camera formats: codd_ingest_pair on frames as a camera, an ISP or a hardware decoder hands
+ * them out, decoded inside the same pass.  The contract is "decode, then ingest": for every format F a decoder
+ * D_F(frame) -> uint8 [h,w,3] RGB is defined below in integer arithmetic, and the outputs are, bit for bit, what
+ *   codd_ingest_pair(D_F(left), D_F(right), h, w, bgr = 0, mean, stdv, maps..., H, W, ...)
+ * writes: the (c - mean)/std expression, the BORDER_REFLECT_101 padding of the DECODED, RECTIFIED image and, with maps,
+ * the bilinear blend of codd_ingest_pair, each of whose four taps is D_F at the integer source pixel (0 outside).  The
+ * decoded image is never written to memory.
+ * A format is named by its bytes in memory; pitch is the bytes per source row, 0 = tight (the row's own bytes):
+ *   CODD_FMT_MONO8        [h][pitch], 1 byte per pixel, R = G = B = the byte;                          h, w >= 1
+ *   CODD_FMT_YUYV         [h][pitch], per pixel pair Y0 U Y1 V (row bytes 2w);                         w even
+ *   CODD_FMT_UYVY         [h][pitch], per pixel pair U Y0 V Y1 (row bytes 2w);                         w even
+ *   CODD_FMT_NV12         Y plane [h][pitch], then at byte pitch*h the interleaved U V plane [h/2][pitch]; w, h even
+ *   CODD_FMT_BAYER_RGGB, _GRBG, _GBRG, _BGGR   [h][pitch], 1 byte per pixel; the name spells the colours of pixels
+ *                         (0,0), (0,1), (1,0), (1,1);                                                  h, w >= 2
+ * codd_frame_bytes: the bytes of one view, pitch * rows with rows = h (3h/2 for NV12); -1 for an unknown format, a
+ * violated size rule, or a pitch that is neither 0 nor >= the row's bytes.  No byte outside [0, codd_frame_bytes) of
+ * either view is read.
+ * YUV -> RGB.  Chroma is nearest, never interpolated: pixel (y,x) takes U, V of its pair x>>1 (NV12: of its block
+ * (y>>1, x>>1)).  int32 arithmetic, >> arithmetic:
+ *   yy = max(Y - yoff, 0) * CY;                         sat8(v) = min(max(v, 0), 255)
+ *   R = sat8((yy + (1<<19) + CVR*(V-128)) >> 20)
+ *   G = sat8((yy + (1<<19) - CUG*(U-128) - CVG*(V-128)) >> 20)
+ *   B = sat8((yy + (1<<19) + CUB*(U-128)) >> 20)
+ * each coefficient the integer nearest to c * 2^20, c from the row that `yuv` selects (ignored for mono and Bayer):
+ *   yuv  name                        yoff  CY     CVR    CUG    CVG    CUB
+ *   0    bt601, video range          16    1.164  1.596  0.391  0.813  2.018   (1220542, 1673527, 409993, 852492,
+ *   1    bt709, video range          16    1.164  1.793  0.213  0.533  2.112    2116026: the integers OpenCV uses)
+ *   2    jpeg, BT.601 full range     0     1.000  1.402  0.344  0.714  1.772
+ * (every accumulator stays below 5.8e8 in magnitude).
+ * Bayer: bilinear demosaic on the 3x3 window of the mosaic extended by reflect-101 (index -1 -> 1, n -> n-2, which
+ * keeps the colour parity; with n = 2 both neighbours are the same pixel).  At an R or B site: own colour = the byte,
+ * G = (N+S+W+E+2)>>2, the opposite colour = (NW+NE+SW+SE+2)>>2.  At a G site: G = the byte, the colour of its row
+ * neighbours = (W+E+1)>>1, the colour of its column neighbours = (N+S+1)>>1.  The mosaic of a flat colour decodes to
+ * exactly that colour at every pixel.
+ * left, right: device, codd_frame_bytes each, ANY alignment; maps, mean / stdv, outputs and the h <= H < 2h, w <= W < 2w
+ * rules as codd_ingest_pair (outputs: float alignment; 16-byte stores only when W % 4 == 0 and the output is 16-byte
+ * aligned).
+ * CODD_EINVAL, before any launch: a NULL image, mean, stdv or output; an unknown fmt; for a YUV format a yuv outside
+ * 0..2; a violated size rule; pitch neither 0 nor >= the row's bytes; one map of a view without the other; a violated
+ * H, W rule. */
+#define CODD_FMT_MONO8 1
+#define CODD_FMT_YUYV 2
+#define CODD_FMT_UYVY 3
+#define CODD_FMT_NV12 4
+#define CODD_FMT_BAYER_RGGB 5
+#define CODD_FMT_BAYER_GRBG 6
+#define CODD_FMT_BAYER_GBRG 7
+#define CODD_FMT_BAYER_BGGR 8
+#define CODD_YUV_BT601 0
+#define CODD_YUV_BT709 1
+#define CODD_YUV_JPEG 2
+int codd_ingest_frames(const unsigned char* left, const unsigned char* right, int fmt, int yuv, int h, int w,
+                       long long pitch, const float* mean, const float* stdv, const float* lmap_x, const float* lmap_y,
+                       const float* rmap_x, const float* rmap_y, int H, int W, float* out_left, float* out_right,
+                       void* stream);
+long long codd_frame_bytes(int fmt, int h, int w, long long pitch);
+
 /* Live-session export: the frame's padded disparity [1,1,H,W] -> the cropped h x w result, contiguous, in a
  * caller-owned device staging buffer (model/codd.py:370-377: `calib / pred_disp` under reciprocal, then the
  * [:img_h, :img_w] crop).  mode:
