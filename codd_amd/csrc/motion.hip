@@ -13,6 +13,7 @@
 // |mean| >> std); the apply kernel combines the partials in fp64 in a fixed order.
 // ------------------------------------------------------------------------------------------------
 #define IN_MAXPARTS 32
+#define IN_STATS_DEPTH 8  // loads a thread of the statistics pass keeps in flight
 __global__ __launch_bounds__(256) void instnorm_stats_kernel(const float* __restrict__ x, int HW, int parts,
                                                              double* __restrict__ partial) {
   __shared__ double red[2][4];
@@ -22,7 +23,20 @@ __global__ __launch_bounds__(256) void instnorm_stats_kernel(const float* __rest
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int per = (HW + parts - 1) / parts, i0 = part * per, i1 = min(HW, i0 + per);
   float s = 0.f, q = 0.f;
-  for (int i = i0 + tid; i < i1; i += 256) { const float d = p[i] - K; s += d; q += d * d; }
+  // a thread's elements i0 + tid + 256 k, added in ascending k: IN_STATS_DEPTH loads are requested before the first is
+  // used (an index past the part reads the part's last element and is dropped by a select)
+  for (int i = i0 + tid; i < i1; i += 256 * IN_STATS_DEPTH) {
+    float v[IN_STATS_DEPTH];
+#pragma unroll
+    for (int k = 0; k < IN_STATS_DEPTH; ++k) v[k] = p[min(i + 256 * k, i1 - 1)];
+#pragma unroll
+    for (int k = 0; k < IN_STATS_DEPTH; ++k) {
+      const bool live = i + 256 * k < i1;
+      const float d = v[k] - K;
+      s = live ? s + d : s;
+      q = live ? fmaf(d, d, q) : q;
+    }
+  }
   double sd = (double)s, qd = (double)q;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { sd += __shfl_xor(sd, o, 64); qd += __shfl_xor(qd, o, 64); }
@@ -34,8 +48,29 @@ __global__ __launch_bounds__(256) void instnorm_stats_kernel(const float* __rest
   }
 }
 
+// A plane's partial sums as lane `lane` of a wave holds them for the combination below (lane = part, 0 past the last
+// part): an unconditional load of a clamped part, so that the request can stand in front of the body's loads.
+struct InPartial { double s, q; };
+__device__ __forceinline__ InPartial instnorm_partial_load(const double* __restrict__ partial, size_t bc, int parts, int lane) {
+  const double* pp = partial + (bc * parts + min(lane, parts - 1)) * 2;
+  return InPartial{pp[0], pp[1]};
+}
+// (mean, rstd) of a plane from its partial sums, one per lane, and its pivot K: the fp64 xor-butterfly in a fixed order,
+// then lane 0's value for the whole wave.  Every wave that is handed the same partials gets the same bits.
+__device__ __forceinline__ void instnorm_combine(InPartial a, int parts, int lane, float K, int HW, float* mean, float* rstd) {
+  double s = lane < parts ? a.s : 0.0, q = lane < parts ? a.q : 0.0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
+  const double md = s / HW;                              // mean of (x - K)
+  const double var = fmax(fma(-md, md, q / HW), 0.0);     // shift invariant
+  *mean = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)((double)K + md))));
+  *rstd = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)(1.0 / sqrt(var + 1e-5)))));
+}
+
 // One workgroup normalises 2048 consecutive elements of one plane (two float4 per thread); the plane's
 // statistics are combined once per workgroup (first wave, fp64 shuffle reduction) instead of once per element.
+// (Two launches a frame.  Requesting the body's vectors in front of the prologue, every wave combining the statistics for
+// itself, measured slower -- 5.9 / 6.1 us against 5.6 us -- and was taken out again: profiles/load_chains_kernels.md.)
 __global__ __launch_bounds__(256) void instnorm_apply_kernel(const float* __restrict__ x,
                                                              const double* __restrict__ partial, int parts,
                                                              const float* __restrict__ res, int HW, int relu,
@@ -93,36 +128,37 @@ __global__ __launch_bounds__(256) void instnorm_apply_xs_kernel(const float* __r
                                                                 const float* __restrict__ res, int C, int H, int W,
                                                                 int relu, int relu2, float* __restrict__ y,
                                                                 const codd_xs_view xs) {
+#pragma clang fp contract(off)  // (v - mean) * rstd and + r stay two roundings wherever the compiler moves them
   __shared__ float st[8][2];
   const int HW = H * W, oct = blockIdx.y, b = blockIdx.z;
   const int bc0 = b * C + oct * 8;
-  if (threadIdx.x < 64) {
-    for (int c = 0; c < 8; ++c) {
-      double s = 0.0, q = 0.0;
-      if ((int)threadIdx.x < parts) {
-        s = partial[((size_t)(bc0 + c) * parts + threadIdx.x) * 2];
-        q = partial[((size_t)(bc0 + c) * parts + threadIdx.x) * 2 + 1];
-      }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // wave w combines the statistics of channels 2w and 2w + 1 of the octet (four independent chains instead of wave 0
+  // walking all eight).  Requested first: their partials and pivots; then, before any of that is waited for, the body's
+  // own 8 (+ 8) values (a pixel past the plane's end reads the plane's last one and is not used).
+  InPartial part[2];
+  float K[2];
 #pragma unroll
-      for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
-      if (threadIdx.x == 0) {
-        const double md = s / HW;
-        const double var = fmax(q / HW - md * md, 0.0);
-        st[c][0] = (float)((double)x[(size_t)(bc0 + c) * HW] + md);
-        st[c][1] = (float)(1.0 / sqrt(var + 1e-5));
-      }
-    }
+  for (int j = 0; j < 2; ++j) {
+    part[j] = instnorm_partial_load(partial, bc0 + 2 * wave + j, parts, lane);
+    K[j] = x[(size_t)(bc0 + 2 * wave + j) * HW];
   }
-  __syncthreads();
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= HW) return;
+  const int i = blockIdx.x * 256 + threadIdx.x, ic = min(i, HW - 1);
   float v[8], r[8];
 #pragma unroll
-  for (int c = 0; c < 8; ++c) v[c] = x[(size_t)(bc0 + c) * HW + i];
+  for (int c = 0; c < 8; ++c) v[c] = x[(size_t)(bc0 + c) * HW + ic];
   if (res) {
 #pragma unroll
-    for (int c = 0; c < 8; ++c) r[c] = res[(size_t)(bc0 + c) * HW + i];
+    for (int c = 0; c < 8; ++c) r[c] = res[(size_t)(bc0 + c) * HW + ic];
   }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    float mean, rstd;
+    instnorm_combine(part[j], parts, lane, K[j], HW, &mean, &rstd);
+    if (lane == 0) { st[2 * wave + j][0] = mean; st[2 * wave + j][1] = rstd; }
+  }
+  __syncthreads();
+  if (i >= HW) return;
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     float t = (v[c] - st[c][0]) * st[c][1];
@@ -447,6 +483,7 @@ extern "C" int codd_raft_geometry(const float* T, const float* depth1, const flo
 #define GN_G2 24  // floats per neighbour PAIR in geo2: [k = 0..11][parity]: X(3) target(3) weight(3) |a|^2 0 0
 #define GN_WAVES 4
 #define GN_SOLVE_WAVES 14  // 27 sums over 14 waves: <= 2 each
+#define GN_SOLVE_BATCH 16  // partials of one sum the solve requests together
 // the pair builder's second record image: [b][y][x / 2][k = 0..11][x & 1], k = X (3), target in
 // normalised image coordinates ((u - cx) / fx, (v - cy) / fy) and inverse depth, weights (wx fx^2, wy fy^2, wz), |a|^2;
 // the phantom partner of the last pixel of an odd-width row is written as zeros (depth 0 = masked, finite)
@@ -910,17 +947,28 @@ __global__ __launch_bounds__(64 * GN_SOLVE_WAVES) void se3_gn_solve_kernel(
     const GnSpan wy = gn_span(ty0, h, radius), wx = gn_span(tx0, w, radius);
     const int G = gn_groups(wy.n() * wx.n(), q4, gmax);
     const float* p = part + (((size_t)b * ntiles + tile) * gmax) * 27 * 64 + lane;
-    for (int k = wave; k < 27; k += GN_SOLVE_WAVES) {
-      float s = 0.f;
-      int g = 0;
-      for (; g + 4 <= G; g += 4) {  // four loads in flight, added in index order
-        const float v0 = p[((size_t)g * 27 + k) * 64], v1 = p[((size_t)(g + 1) * 27 + k) * 64];
-        const float v2 = p[((size_t)(g + 2) * 27 + k) * 64], v3 = p[((size_t)(g + 3) * 27 + k) * 64];
-        s = (((s + v0) + v1) + v2) + v3;
+    // a wave's two sums, k0 = wave and k1 = wave + 14 (the last wave has one: its second chain re-reads row 26 and is
+    // dropped), GN_SOLVE_BATCH partials of each requested together and added in index order -- G = 27 is two rounds.
+    // A group past G reads group G - 1 and is dropped by a select.
+    const int k0 = wave, k1 = wave + GN_SOLVE_WAVES, k1c = min(k1, 26);
+    float s0 = 0.f, s1 = 0.f;
+    for (int g0 = 0; g0 < G; g0 += GN_SOLVE_BATCH) {
+      float a[GN_SOLVE_BATCH], c[GN_SOLVE_BATCH];
+#pragma unroll
+      for (int j = 0; j < GN_SOLVE_BATCH; ++j) {
+        const int g = min(g0 + j, G - 1);
+        a[j] = p[((size_t)g * 27 + k0) * 64];
+        c[j] = p[((size_t)g * 27 + k1c) * 64];
       }
-      for (; g < G; ++g) s += p[((size_t)g * 27 + k) * 64];
-      sums[k][lane] = s;
+#pragma unroll
+      for (int j = 0; j < GN_SOLVE_BATCH; ++j) {
+        const bool live = g0 + j < G;
+        s0 = live ? s0 + a[j] : s0;
+        s1 = live ? s1 + c[j] : s1;
+      }
     }
+    sums[k0][lane] = s0;
+    if (k1 < 27) sums[k1][lane] = s1;
   }
   __syncthreads();
   if (wave != 0) return;
@@ -1228,12 +1276,19 @@ struct SplatP {
   float4* uvz;  // per source point: projected (u, v, z, valid) written by the count pass
 };
 
-__device__ __forceinline__ bool splat_point(const SplatP& p, int b, int n, float* u, float* v, float* z,
-                                            V3* flow) {
+// what a source point reads: its pose and depth (the gather pass requests those of several points before it uses any)
+struct SplatSrc { SE3T Ti; float depth; int px, py; };
+__device__ __forceinline__ SplatSrc splat_src_load(const SplatP& p, int b, int n) {
   const int py = n / p.W, px = n - py * p.W;
   const size_t src = (size_t)b * p.HT * p.WT + (size_t)(p.oy + p.ds * py) * p.WT + (p.ox + p.ds * px);
-  const SE3T Ti = se3_load(p.T + src * 7);
-  const V3 X0 = inv_project(p.depth[src], px, py, p.fx, p.fy, p.cx, p.cy);
+  return SplatSrc{se3_load(p.T + src * 7), p.depth[src], px, py};
+}
+
+__device__ __forceinline__ bool splat_point(const SplatP& p, const SplatSrc& sp, float* u, float* v, float* z,
+                                            V3* flow) {
+  const SE3T Ti = sp.Ti;
+  const int px = sp.px, py = sp.py;
+  const V3 X0 = inv_project(sp.depth, px, py, p.fx, p.fy, p.cx, p.cy);
   const V3 X1 = se3_act(Ti, X0);
   *z = X1.z;
   if (!(X1.z > 0.f)) return false;
@@ -1277,7 +1332,7 @@ __global__ void splat_count_kernel(const SplatP p) {
   const int b = blockIdx.y;
   if (n >= p.H * p.W) return;
   float u = 0.f, v = 0.f, z = 0.f;
-  const bool ok = splat_point(p, b, n, &u, &v, &z, nullptr);
+  const bool ok = splat_point(p, splat_src_load(p, b, n), &u, &v, &z, nullptr);
   p.uvz[(size_t)b * p.H * p.W + n] = make_float4(u, v, z, ok ? 1.f : 0.f);
   if (!ok) return;
   splat_cover(p, b, u, v, [&](size_t pix) { atomicAdd(&p.cnt[pix], 1); });
@@ -1332,7 +1387,41 @@ __global__ void splat_fill_kernel(const SplatP p) {
   splat_cover(p, b, q.x, q.y, [&](size_t pix) { p.list[p.off[pix] + atomicAdd(&p.cur[pix], 1)] = n; });
 }
 
+// A loaded value stays where the source requested it: without this the compiler moves a load whose value only one side of
+// a later select or branch uses down into that side, behind a wait for every load before it.
+__device__ __forceinline__ void splat_keep_loaded(float& v) { asm volatile("" : "+v"(v)); }
+#define SPLAT_CAND_BATCH 8  // candidate ids (then records) the gather pass requests together
+#define SPLAT_FEAT_BATCH 4  // feature channels whose 8 slot values are requested before the first result is stored
+// op[c * HW] = sum over the nk occupied slots of wk[k] * feat[b][c][kid[k]], c < Cf (feat may be null when Cf is 0).
+// Every slot is read (kid[k] is 0 past nk) and dropped by a select on the RESULT: adding a zero product instead would
+// turn a -0 sum into +0 and let a NaN at feat[..][0] in.  The last batch re-reads channel Cf - 1 and does not store it.
+__device__ __forceinline__ void splat_gather_feat(const float* feat, int Cf, int b, int HW, const int (&kid)[8],
+                                                  const float (&wk)[8], int nk, float* op) {
+  for (int c0 = 0; c0 < Cf; c0 += SPLAT_FEAT_BATCH) {
+    float f[SPLAT_FEAT_BATCH][8];
+#pragma unroll
+    for (int j = 0; j < SPLAT_FEAT_BATCH; ++j) {
+      const float* fp = feat + ((size_t)b * Cf + min(c0 + j, Cf - 1)) * HW;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) f[j][k] = fp[kid[k]];
+    }
+#pragma unroll
+    for (int j = 0; j < SPLAT_FEAT_BATCH; ++j) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) splat_keep_loaded(f[j][k]);
+    }
+#pragma unroll
+    for (int j = 0; j < SPLAT_FEAT_BATCH; ++j) {
+      float acc = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc = k < nk ? fmaf(wk[k], f[j][k], acc) : acc;
+      if (c0 + j < Cf) op[(size_t)(c0 + j) * HW] = acc;
+    }
+  }
+}
+
 __global__ void splat_gather_kernel(const SplatP p) {
+#pragma clang fp contract(off)  // the multiply-adds of this body are spelled fmaf
   // XCD-contiguous walk (common.h codd_xcd_item): a 256-pixel row segment's candidates are the points that landed within
   // R of it -- the same uvz records, pose / depth and feature lines the segments of the rows above and below read.
   // With the dispatcher's block -> XCD b % 8 placement those neighbours sit on eight different L2s (round 4: 75 MB per
@@ -1353,20 +1442,30 @@ __global__ void splat_gather_kernel(const SplatP p) {
   for (int q = 0; q < 8; ++q) { kz[q] = INFINITY; ka[q] = 0.f; kid[q] = 0x7fffffff; }
   int nk = 0;
   const float R2 = p.R * p.R;
-  for (int s = 0; s < cnt; ++s) {
-    const int n = lp[s];
-    // 16 bytes written by pass 1 instead of re-loading T (28 B) + depth and redoing the SE3 action per candidate
-    const float4 q4 = p.uvz[(size_t)b * HW + n];
-    const float du = q4.x - ((float)px + 0.5f), dv = q4.y - ((float)py + 0.5f);
-    float cz = q4.z, ca = 1.f - splat_d2(du, dv) / R2;
-    int cn = n;
-    // insertion by carrying the displaced element down the list
+  // candidates in batches: the ids of a batch, then their records together, then the insertions in list order (a slot
+  // past the list's end reads the list's last id again and is not inserted)
+  for (int s0 = 0; s0 < cnt; s0 += SPLAT_CAND_BATCH) {
+    int bn[SPLAT_CAND_BATCH];
+    float4 bq[SPLAT_CAND_BATCH];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      if (cz < kz[q] || (cz == kz[q] && cn < kid[q])) {
+    for (int j = 0; j < SPLAT_CAND_BATCH; ++j) bn[j] = lp[min(s0 + j, cnt - 1)];
+    // 16 bytes written by pass 1 instead of re-loading T (28 B) + depth and redoing the SE3 action per candidate
+#pragma unroll
+    for (int j = 0; j < SPLAT_CAND_BATCH; ++j) bq[j] = p.uvz[(size_t)b * HW + bn[j]];
+#pragma unroll
+    for (int j = 0; j < SPLAT_CAND_BATCH; ++j) {
+      const bool live = s0 + j < cnt;
+      const float4 q4 = bq[j];
+      const float du = q4.x - ((float)px + 0.5f), dv = q4.y - ((float)py + 0.5f);
+      float cz = q4.z, ca = 1.f - splat_d2(du, dv) / R2;
+      int cn = bn[j];
+      // insertion by carrying the displaced element down the list
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const bool ins = live & ((cz < kz[q]) | ((cz == kz[q]) & (cn < kid[q])));  // (no short circuit: no branches)
         const float tz = kz[q], ta = ka[q]; const int tn = kid[q];
-        kz[q] = cz; ka[q] = ca; kid[q] = cn;
-        cz = tz; ca = ta; cn = tn;
+        kz[q] = ins ? cz : tz; ka[q] = ins ? ca : ta; kid[q] = ins ? cn : tn;
+        cz = ins ? tz : cz; ca = ins ? ta : ca; cn = ins ? tn : cn;
       }
     }
   }
@@ -1378,34 +1477,38 @@ __global__ void splat_gather_kernel(const SplatP p) {
 #pragma unroll
   for (int k = 0; k < 8; ++k) { wk[k] = k < nk ? tr * ka[k] : 0.f; tr *= (1.f - ka[k]); if (k >= nk) kid[k] = 0; }
   float* op = p.out + (size_t)b * C * HW + pix;
-  for (int c = 0; c < p.CA; ++c) {
-    const float* fp = p.featA + ((size_t)b * p.CA + c) * HW;
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) if (k < nk) acc += wk[k] * fp[kid[k]];
-    op[(size_t)c * HW] = acc;
-  }
+  splat_gather_feat(p.featA, p.CA, b, HW, kid, wk, nk, op);
   int co = p.CA;
   if (p.with_flow) {
     float f0 = 0.f, f1 = 0.f, f2 = 0.f;
+    // pose and depth of four slots requested before the first SE3 action (an empty slot reads source point 0)
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if (k < nk) {
-        float u, v, z; V3 fl;
-        splat_point(p, b, kid[k], &u, &v, &z, &fl);
-        f0 += wk[k] * fl.x; f1 += wk[k] * fl.y; f2 += wk[k] * fl.z;
+    for (int k0 = 0; k0 < 8; k0 += 4) {
+      if (k0 >= nk) continue;
+      SplatSrc sp[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sp[j] = splat_src_load(p, b, kid[k0 + j]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        splat_keep_loaded(sp[j].Ti.t.x); splat_keep_loaded(sp[j].Ti.t.y); splat_keep_loaded(sp[j].Ti.t.z);
+        splat_keep_loaded(sp[j].Ti.q.x); splat_keep_loaded(sp[j].Ti.q.y); splat_keep_loaded(sp[j].Ti.q.z);
+        splat_keep_loaded(sp[j].Ti.q.w); splat_keep_loaded(sp[j].depth);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = k0 + j;
+        float u, v, z;
+        V3 fl = V3{0.f, 0.f, 0.f};
+        splat_point(p, sp[j], &u, &v, &z, &fl);
+        f0 = k < nk ? fmaf(wk[k], fl.x, f0) : f0;
+        f1 = k < nk ? fmaf(wk[k], fl.y, f1) : f1;
+        f2 = k < nk ? fmaf(wk[k], fl.z, f2) : f2;
       }
     }
     op[(size_t)co * HW] = f0; op[(size_t)(co + 1) * HW] = f1; op[(size_t)(co + 2) * HW] = f2;
     co += 3;
   }
-  for (int c = 0; c < p.CB; ++c) {
-    const float* fp = p.featB + ((size_t)b * p.CB + c) * HW;
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) if (k < nk) acc += wk[k] * fp[kid[k]];
-    op[(size_t)(co + c) * HW] = acc;
-  }
+  splat_gather_feat(p.featB, p.CB, b, HW, kid, wk, nk, op + (size_t)co * HW);
   if (p.zout) {
     const float zn = nk > 0 ? fmaxf(kz[0], 0.f) : 0.f;
     float o = zn;
