@@ -52,6 +52,11 @@ class RollParams(C.Structure):
                 ("rh", C.c_int)]
 
 
+class CalibView(C.Structure):  # codd_calib_view
+    _fields_ = [("R", C.c_double * 9), ("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("K", C.c_double * 4),
+                ("dist", C.c_double * 8), ("model", C.c_int)]
+
+
 _i, _f, _p, _ll = C.c_int, C.c_float, C.c_void_p, C.c_longlong
 
 # name -> (restype, argtypes); must list every function declared in include/codd_hip.h
@@ -123,6 +128,9 @@ SIGNATURES = {
     "codd_ingest_pair": (_i, [_p, _p, _i, _i, _i, c_float_p, c_float_p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
     "codd_ingest_frames": (_i, [_p, _p, _i, _i, _i, _i, _ll, c_float_p, c_float_p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
     "codd_frame_bytes": (_ll, [_i, _i, _i, _ll]),
+    "codd_rectify_maps": (_i, [C.POINTER(CalibView), C.POINTER(CalibView), _i, _i, _p, _p, _p, _p, _p]),
+    "codd_ingest_calibrated": (_i, [_p, _p, _i, _i, _i, _i, _i, _ll, C.POINTER(CalibView), C.POINTER(CalibView), _i, _i,
+                                    c_float_p, c_float_p, _i, _i, _p, _p, _p]),
     "codd_export_depth": (_i, [_p, _i, _i, _i, _i, _i, _f, _p, _p]),
     "codd_export_motion": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p]),
     "codd_ego_motion_scratch": (_ll, [_i, _i]),

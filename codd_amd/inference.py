@@ -55,6 +55,12 @@ def parse_args(argv=None):
     p.add_argument("--occ-px", type=float, default=None, help="--confidence: occlusion tolerance in pixels (default 1.0)")
     p.add_argument("--tau", type=float, default=None, help="--confidence: mismatch threshold in grey levels (default 24.0)")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
+    p.add_argument("--calibration", help="--live: .json / .npz stereo calibration (or rectification) of the rig, see "
+                   "INTEGRATION.md; the frames are rectified from it on the GPU, and intrinsics and calib are those of the "
+                   "rectified camera.  Exclusive with --rectify-maps")
+    p.add_argument("--zoom", type=float, default=None, help="--calibration: scale of the rectified focal length (default 1.0)")
+    p.add_argument("--net-size", default=None, metavar="HxW", help="--calibration: height x width of the rectified image "
+                   "the network sees (default: the size of the source frames)")
     p.add_argument("--pixel-format", choices=list(ops.FRAME_FORMATS), default=None,
                    help="--live: the frame files are raw byte dumps in this camera format (what `v4l2-ctl --stream-to` "
                    "writes, one frame per file, selected by --img-suffix), decoded on the GPU; needs --frame-size")
@@ -73,6 +79,18 @@ def parse_args(argv=None):
         args.frame_size = (int(m.group(1)), int(m.group(2)))
     elif args.frame_size is not None or args.pitch is not None or args.yuv is not None:
         p.error("--frame-size / --pitch / --yuv need --pixel-format")
+    if args.calibration is not None:
+        if not args.live:
+            p.error("--calibration needs --live")
+        if args.rectify_maps:
+            p.error("--calibration and --rectify-maps exclude each other")
+        if args.net_size is not None:
+            m = re.fullmatch(r"(\d+)x(\d+)", args.net_size)
+            if not m:
+                p.error("--net-size: HxW expected")
+            args.net_size = (int(m.group(1)), int(m.group(2)))
+    elif args.zoom is not None or args.net_size is not None:
+        p.error("--zoom / --net-size need --calibration")
     if args.motion is not None and not args.live:
         p.error("--motion needs --live")
     if args.ego and not args.live:
@@ -234,7 +252,8 @@ def run_live(args, model, videos):
     <name>.motion.pred.npz ([1, frames, h, w, C]; a frame without a field is all NaN) and, with --ego,
     <name>.ego.pred.npz (pose, stats, camera_to_world, moving; a frame without a field is NaN, 255 in moving) and, with
     --confidence, <name>.conf.pred.npz (flags and residual, [1, frames, h, w] each).  With --pixel-format the frame files
-    are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU."""
+    are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU.  With
+    --calibration the frames (files or --frame-size) have the calibration's source size and every result has --net-size."""
     from PIL import Image
     from .live import LiveSession
     maps = None
@@ -249,12 +268,19 @@ def run_live(args, model, videos):
         extra.update(pixel_format=raw, pitch=args.pitch, yuv=args.yuv or "bt601")
     sessions = {}
     for name, lefts, rights in videos:
-        h, w = args.frame_size if raw else Image.open(lefts[0]).size[::-1]
+        src = h, w = args.frame_size if raw else Image.open(lefts[0]).size[::-1]
+        cal = getattr(args, "calibration", None)
+        if cal:
+            h, w = args.net_size or src
+            rig = dict(calibration=cal, zoom=1.0 if args.zoom is None else args.zoom)
+        else:
+            rig = dict(intrinsics=CUSTOM["intrinsics"], calib=CUSTOM["calib"], rectify=maps)
         s = sessions.get((h, w))
         if s is None:
-            s = sessions[(h, w)] = LiveSession(model, (h, w), intrinsics=CUSTOM["intrinsics"], calib=CUSTOM["calib"],
-                                               output=args.output, bgr=False, rectify=maps, use_graph=not args.no_graph,
-                                               motion=args.motion, **extra)
+            s = sessions[(h, w)] = LiveSession(model, (h, w), output=args.output, bgr=False, use_graph=not args.no_graph,
+                                               motion=args.motion, **rig, **extra)
+        if cal and s.src_shape != tuple(src):
+            raise ValueError(f"{name}: frames of {src[0]}x{src[1]}, the calibration is for {s.src_shape[0]}x{s.src_shape[1]}")
         s.reset()
         out = mot = ego = cflags = cres = None
         nf = len(lefts)
@@ -275,7 +301,7 @@ def run_live(args, model, videos):
                 cres = cflags.spool("residual", (1, nf, h, w), np.float32)
         n = 0
         try:
-            frames = iter_raw_frames(lefts, rights, raw, (h, w), args.pitch) if raw else iter_frames(lefts, rights)
+            frames = iter_raw_frames(lefts, rights, raw, src, args.pitch) if raw else iter_frames(lefts, rights)
             for res in live_results(s, frames):
                 n += 1
                 if args.confidence:

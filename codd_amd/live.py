@@ -30,13 +30,18 @@ With ``pixel_format=`` the session takes frames as a camera hands them out -- mo
 with a row pitch -- uploads those bytes (1 to 2 per pixel instead of 3) and decodes them inside the ingest launch:
 ``codd_ingest_frames`` stands where ``codd_ingest_pair`` stands above and writes the bits ``codd_ingest_pair`` writes on
 the decoded RGB images, so that everything behind it is unchanged.
+
+With ``calibration=`` the session rectifies from the rig's calibration (codd_amd/calibration.py): ``shape`` is the size
+of the rectified image the network sees, frames arrive at the calibration's own source size in either family of formats,
+and ``codd_ingest_calibrated`` stands where the two entries above stand -- it evaluates the rectifying map in registers
+(no map arrays) -- while ``intrinsics`` and ``calib`` of the rectified virtual camera come from the rectification.
 """
 from collections import deque, namedtuple
 
 import numpy as np
 import torch
 
-from . import _abi, ops, synth
+from . import _abi, calibration as _calibration, ops, synth
 from .runtime import FrameRunner
 
 OUTPUTS = ("disp", "depth", "disp_u16")
@@ -44,6 +49,7 @@ MOTIONS = ("flow2d", "flow_dd", "sceneflow")
 PIXEL_FORMATS = ("rgb8",) + tuple(ops.FRAME_FORMATS)  # rgb8: packed [h,w,3] through codd_ingest_pair; the others raw
 YUVS = tuple(ops.YUV_MATRICES)
 DEPTH = 2  # frames in flight: input, device and host output slots are double-buffered
+DEFAULT_INTRINSICS, DEFAULT_CALIB = (1050.0, 1050.0, 480.0, 270.0), 210.0  # without calibration= and not passed
 EGO_DEFAULTS = dict(iters=5, delta_px=1.0, tau_px=2.0, min_valid=16)
 CONF_DEFAULTS = dict(occ_px=1.0, tau=24.0)
 
@@ -257,11 +263,17 @@ class LiveSession:
     Y plane and the interleaved U V plane behind it.  ``pitch`` (bytes per row, None: tight) and ``yuv`` ("bt601" and
     "bt709" video range, "jpeg" full range) describe the source; ``bgr`` and ``pitch`` do not combine with the other
     family of formats (ValueError).  The decode is defined in include/codd_hip.h (codd_ingest_frames).
+
+    ``calibration`` (a ``calibration.StereoCalibration``, a ``calibration.Rectification``, or a path to a ``.json`` /
+    ``.npz`` file of either) with ``zoom``: ``shape`` is then the size of the RECTIFIED image (what the network sees and
+    what every result has), frames have the calibration's source size (``src_shape``; ``pitch`` and the format's size
+    rules apply to it), and ``intrinsics`` and ``calib`` are those of the rectified virtual camera -- passing either, or
+    ``rectify=``, next to ``calibration`` is a ValueError.  The map is defined in include/codd_hip.h (THE MAP FUNCTION).
     """
 
-    def __init__(self, estimator, shape, intrinsics=(1050.0, 1050.0, 480.0, 270.0), calib=210.0, output="depth",
+    def __init__(self, estimator, shape, intrinsics=None, calib=None, output="depth",
                  bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False,
-                 pixel_format="rgb8", yuv="bt601", pitch=None):
+                 pixel_format="rgb8", yuv="bt601", pitch=None, calibration=None, zoom=1.0):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
@@ -277,7 +289,21 @@ class LiveSession:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
         if yuv not in YUVS:
             raise ValueError(f"yuv: one of {YUVS} expected, got {yuv!r}")
-        self._layout = frame_layout(pixel_format, h, w, pitch)  # (rows, row_bytes, pitch, nbytes); ValueError if invalid
+        self.rect = None
+        if calibration is not None:
+            for name, given in (("intrinsics", intrinsics), ("calib", calib), ("rectify", rectify)):
+                if given is not None:
+                    raise ValueError(f"{name}: not together with calibration= (the rectification provides it)")
+            self.rect = _calibration.resolve(calibration, (h, w), zoom)
+            intrinsics, calib = self.rect.intrinsics, self.rect.calib
+            self._calib_views = ops.calib_structs(self.rect)  # (ctypes structs: no device call)
+        elif float(zoom) != 1.0:
+            raise ValueError("zoom: needs calibration=")
+        intrinsics = DEFAULT_INTRINSICS if intrinsics is None else intrinsics
+        calib = DEFAULT_CALIB if calib is None else calib
+        self.src_shape = (h, w) if self.rect is None else self.rect.size  # the size of a frame as the camera hands it out
+        # (rows, row_bytes, pitch, nbytes) of a source frame; ValueError if invalid
+        self._layout = frame_layout(pixel_format, self.src_shape[0], self.src_shape[1], pitch)
         if pixel_format != "rgb8" and bgr:
             raise ValueError(f"bgr=True is for rgb8 frames only (pixel_format={pixel_format!r} names its own byte order)")
         self.pixel_format, self.yuv, self.pitch = pixel_format, yuv, None if pitch is None else int(pitch)
@@ -311,7 +337,7 @@ class LiveSession:
         odt = torch.int16 if self.output == "disp_u16" else torch.float32  # (uint16 bits; handed out as numpy uint16)
         with torch.cuda.device(dev):
             # rgb8: [h,w,3]; a raw format: the frame's bytes, flat (frame_layout: rows x pitch)
-            slot = (h, w, 3) if self.pixel_format == "rgb8" else (self._layout[3],)
+            slot = self.src_shape + (3,) if self.pixel_format == "rgb8" else (self._layout[3],)
             self._h_in = [[torch.empty(slot, dtype=torch.uint8, pin_memory=True) for _ in range(2)] for _ in range(DEPTH)]
             self._d_in = [[torch.empty(slot, dtype=torch.uint8, device=dev) for _ in range(2)] for _ in range(DEPTH)]
             self._scratch = tuple(torch.empty(1, 3, H, W, dtype=torch.float32, device=dev) for _ in range(2))
@@ -353,9 +379,9 @@ class LiveSession:
         raw = self.pixel_format != "rgb8"
         for a, name in ((left_u8, "left"), (right_u8, "right")):
             if raw:
-                check_raw_frame(a, self.pixel_format, self.shape, self.pitch, name)
+                check_raw_frame(a, self.pixel_format, self.src_shape, self.pitch, name)
             else:
-                check_frame(a, self.shape, name)
+                check_frame(a, self.src_shape, name)
         if not self._open_done:
             self._open()
         if len(self._inflight) == DEPTH:
@@ -385,7 +411,11 @@ class LiveSession:
 
             def fill(left, right):
                 images[:] = (left, right)  # (the frame's normalised images: read again by export_confidence)
-                if raw:
+                if self.rect is not None:
+                    ops.ingest_calibrated(self._d_in[k][0], self._d_in[k][1], left, right, self._calib_views,
+                                          self.pixel_format, self.src_shape, self.shape, bgr=self.bgr, yuv=self.yuv,
+                                          pitch=self.pitch)
+                elif raw:
                     ops.ingest_frames(self._d_in[k][0], self._d_in[k][1], left, right, self.pixel_format, self.shape,
                                       yuv=self.yuv, pitch=self.pitch, maps=self._maps)
                 else:

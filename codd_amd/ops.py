@@ -1795,6 +1795,89 @@ def ingest_frames(left_u8, right_u8, out_left, out_right, fmt, shape, yuv="bt601
                                       _stream()), "ingest_frames")
 
 
+CALIB_MODELS = dict(brown=0, fisheye=1)  # CODD_CALIB_* of include/codd_hip.h
+CALIB_FORMATS = dict(rgb8=0, **FRAME_FORMATS)  # CODD_FMT_RGB8 next to the raw formats
+
+
+def calib_structs(rect):
+    """The two ``codd_calib_view`` structs of a ``calibration.Rectification`` -- or of a pair ``(left, right)`` of
+    ``calibration.RectifiedView``s, either of which may be None (a view without calibration) -- as a tuple that
+    ``rectify_maps`` and ``ingest_calibrated`` also take in place of ``rect``.  No device call."""
+    if isinstance(rect, tuple) and len(rect) == 2 and all(v is None or isinstance(v, _abi.CalibView) for v in rect):
+        return rect
+    views = rect.views if hasattr(rect, "views") else tuple(rect)
+    if len(views) != 2:
+        raise ValueError("rect: a Rectification or a pair (left view, right view) expected")
+    out = []
+    for v in views:
+        if v is None:
+            out.append(None)
+            continue
+        s = _abi.CalibView()
+        s.R[:] = [float(x) for row in v.R for x in row]
+        s.f, s.cx, s.cy = float(v.P[0]), float(v.P[2]), float(v.P[3])
+        s.K[:] = v.camera.K
+        s.dist[:] = v.camera.dist8
+        s.model = CALIB_MODELS[v.camera.model]
+        out.append(s)
+    return tuple(out)
+
+
+def rectify_maps(rect, shape, device):
+    """The rectifying maps of ``rect`` (as ``calib_structs`` takes it) for a rectified image of ``shape`` (h, w), computed
+    on ``device``: ``((lmx, lmy), (rmx, rmy))``, fp32 [h,w] each -- what ``ingest_pair`` / ``ingest_frames`` take as
+    ``maps`` and what ``cv2.remap`` takes; a view without calibration gives None in place of its pair."""
+    lib = _abi.load()
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _abi.CoddHipError("codd_amd ops run on ROCm devices only (no CPU fallback in the product path)")
+    views = calib_structs(rect)
+    h, w = int(shape[0]), int(shape[1])
+    with torch.cuda.device(device):
+        maps = tuple(None if v is None else tuple(torch.empty(h, w, dtype=torch.float32, device=device) for _ in range(2))
+                     for v in views)
+        ptrs = [None if p is None else m.data_ptr() for p in maps for m in (p or (None, None))]
+        _abi.check(lib.codd_rectify_maps(*(None if v is None else C.byref(v) for v in views), h, w, *ptrs, _stream()),
+                   "rectify_maps")
+    return maps
+
+
+def ingest_calibrated(left_u8, right_u8, out_left, out_right, rect, fmt, src_shape, shape, bgr=False, yuv="bt601",
+                      pitch=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """``ingest_pair`` (``fmt`` "rgb8", with ``bgr``) and ``ingest_frames`` (a key of FRAME_FORMATS) in one launch that
+    rectifies from a calibration: both views, uint8 device tensors of a ``src_shape`` = (hs, ws) frame in format ``fmt``
+    (``pitch``: bytes per source row, None = tight), are sampled at the positions the map function of ``rect`` (as
+    ``calib_structs`` takes it) gives for a rectified image of ``shape`` = (h, w), and written normalised and
+    reflect-padded into the caller's [..,3,H,W] buffers -- the bits ``ingest_pair`` / ``ingest_frames`` give with the maps
+    of ``rectify_maps(rect, shape)``, which are never in memory here.  A view without calibration takes the map-free
+    path (then ``src_shape`` must equal ``shape``)."""
+    lib = _abi.load()
+    _require_gpu(left_u8)
+    if fmt not in CALIB_FORMATS:
+        raise ValueError(f"pixel format: one of {tuple(CALIB_FORMATS)} expected, got {fmt!r}")
+    if yuv not in YUV_MATRICES:
+        raise ValueError(f"yuv: one of {tuple(YUV_MATRICES)} expected, got {yuv!r}")
+    hs, ws = int(src_shape[0]), int(src_shape[1])
+    h, w = int(shape[0]), int(shape[1])
+    if fmt == "rgb8":
+        if hs <= 0 or ws <= 0 or (pitch is not None and int(pitch) < 3 * ws):
+            raise ValueError(f"rgb8: invalid size {hs}x{ws} or pitch {pitch}")
+        nbytes = hs * (3 * ws if pitch is None else int(pitch))
+    else:
+        nbytes = frame_bytes(fmt, hs, ws, pitch)
+    views = calib_structs(rect)
+    for t in (left_u8, right_u8):
+        assert t.dtype == torch.uint8 and t.numel() == nbytes and t.is_contiguous() and t.is_cuda
+    H, W = out_left.shape[-2:]
+    for t in (out_left, out_right):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and t.numel() == 3 * H * W
+    m, s = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    _abi.check(lib.codd_ingest_calibrated(left_u8.data_ptr(), right_u8.data_ptr(), CALIB_FORMATS[fmt], int(bool(bgr)),
+                                          YUV_MATRICES[yuv], hs, ws, int(pitch or 0),
+                                          *(None if v is None else C.byref(v) for v in views), h, w, m, s, H, W,
+                                          out_left.data_ptr(), out_right.data_ptr(), _stream()), "ingest_calibrated")
+
+
 EXPORT_MODES = dict(disp=0, depth=1, disp_u16=2)  # CODD_EXPORT_* of include/codd_hip.h
 
 

@@ -618,6 +618,75 @@ int codd_ingest_frames(const unsigned char* left, const unsigned char* right, in
                        void* stream);
 long long codd_frame_bytes(int fmt, int h, int w, long long pitch);
 
+/* Rectification from a stereo calibration (codd_amd/calibration.py, LiveSession(calibration=)): the rectifying map as a
+ * closed-form function of one view's calibration, written out as map arrays (codd_rectify_maps) or evaluated in
+ * registers inside the ingest launch (codd_ingest_calibrated).
+ * One view is described by a codd_calib_view, all doubles: R, the rectifying rotation R_rect (row-major, X_rect = R_rect
+ * X_cam); f, cx, cy, the rectified pinhole camera (f' = fx' = fy', cx', cy'); K = (fx, fy, cx, cy) and dist, the source
+ * camera; model, CODD_CALIB_BROWN (dist = k1 k2 p1 p2 k3 k4 k5 k6, OpenCV's rational model) or CODD_CALIB_FISHEYE
+ * (dist = k1 k2 k3 k4 of Kannala-Brandt as cv2.fisheye, dist[4..7] ignored).
+ * THE MAP FUNCTION.  Rectified pixel (u, v) of a view maps to the source position (sx, sy):
+ *   xr = (u - cx') / f',  yr = (v - cy') / f'
+ *   (X, Y, W) = R_rect^T (xr, yr, 1);   W <= 0 or non-finite  ->  (sx, sy) = NaN   (the pixel reads 0)
+ *   x = X / W, y = Y / W, r2 = x^2 + y^2
+ *   brown:   kr = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3)
+ *            xd = x kr + 2 p1 x y + p2 (r2 + 2 x^2),   yd = y kr + p1 (r2 + 2 y^2) + 2 p2 x y
+ *   fisheye: r = sqrt(r2), t = atan(r), td = t (1 + k1 t^2 + k2 t^4 + k3 t^6 + k4 t^8), s = r > 1e-8 ? td / r : 1,
+ *            xd = x s, yd = y s
+ *   sx = fx xd + cx,  sy = fy yd + cy
+ * The constants.  The entry computes them on the host in fp64 and rounds each ONCE to fp32: the nine entries of
+ * M = R_rect^T K'^-1, so that (X, Y, W) = M (u, v, 1):
+ *   m[3i] = R[0][i] / f',  m[3i+1] = R[1][i] / f',  m[3i+2] = R[2][i] - (R[0][i] cx' + R[1][i] cy') / f'     (i = 0, 1, 2)
+ * and fx, fy, cx, cy, dist[0..7].
+ * The fp32 operation order of the kernels (fma = one fused multiply-add, every other operation rounded to nearest on
+ * its own; u, v the pixel's integer coordinates as floats; division and sqrt correctly rounded; atan is atanf):
+ *   X = fma(m0, u, fma(m1, v, m2));  Y = fma(m3, u, fma(m4, v, m5));  W = fma(m6, u, fma(m7, v, m8))
+ *   !(0 < W < +inf)  ->  sx = sy = NaN
+ *   iw = 1 / W;  x = X * iw;  y = Y * iw;  xx = x * x;  yy = y * y;  r2 = fma(y, y, xx)
+ *   brown:   num = fma(fma(fma(k3, r2, k2), r2, k1), r2, 1);  den = fma(fma(fma(k6, r2, k5), r2, k4), r2, 1)
+ *            kr = num / den;  xy2 = (x + x) * y
+ *            xd = fma(x, kr, fma(p1, xy2, p2 * fma(2, xx, r2)));  yd = fma(y, kr, fma(p2, xy2, p1 * fma(2, yy, r2)))
+ *   fisheye: r = sqrt(r2);  t = atanf(r);  t2 = t * t
+ *            td = t * fma(fma(fma(fma(k4, t2, k3), t2, k2), t2, k1), t2, 1);  s = r > 1e-8f ? td / r : 1
+ *            xd = x * s;  yd = y * s
+ *   sx = fma(fx, xd, cx);  sy = fma(fy, yd, cy)
+ * A value that overflows on the way (a pixel near the W = 0 horizon) ends as inf or NaN and reads 0 like any
+ * non-finite map entry.
+ *
+ * codd_rectify_maps writes map_x, map_y (fp32 [h,w], device) of each view whose struct is not NULL -- exactly the maps
+ * codd_ingest_pair / codd_ingest_frames take, and what cv2.remap takes.  CODD_EINVAL before any launch: both structs
+ * NULL; h or w <= 0; a map pointer NULL for a view that has a struct; an unknown model; a non-finite entry in a struct;
+ * f', fx or fy not positive.
+ *
+ * codd_ingest_calibrated is codd_ingest_pair (fmt = CODD_FMT_RGB8: packed [hs][pitch] rows of 3-byte pixels, row bytes
+ * 3 ws, with bgr) and codd_ingest_frames (the eight raw formats; bgr ignored) in one entry whose source frame has a
+ * size of its own: the source is hs x ws (the format size rules, pitch and codd_frame_bytes apply to hs, ws), the
+ * rectified image h x w, the padded output H x W.  Each tap position comes from the map function above, evaluated in
+ * registers.  THE CONTRACT: each output is, bit for bit, the bilinear blend of codd_ingest_pair / codd_ingest_frames
+ * taken at the (sx, sy) codd_rectify_maps writes for the same struct: a tap outside the hs x ws source contributes 0, the
+ * blend is fp32 and unrounded, then (c - mean) / std, and the border is the BORDER_REFLECT_101 padding of the RECTIFIED
+ * image.  A view whose struct is NULL takes the map-free path (then hs, ws must equal h, w).
+ * CODD_EINVAL before any launch: a NULL image, output, mean or stdv; both structs NULL; an unknown fmt, for a YUV format
+ * a yuv outside 0..2, an unknown model; a violated format size rule on hs, ws; pitch neither 0 nor >= the row's bytes;
+ * h or w <= 0 or a violated h <= H < 2h, w <= W < 2w; a struct with a non-finite entry or with f', fx or fy not
+ * positive; a NULL struct with (hs, ws) != (h, w). */
+enum { CODD_FMT_RGB8 = 0 }; /* this entry only: not one of the raw formats codd_ingest_frames / codd_frame_bytes take */
+#define CODD_CALIB_BROWN 0
+#define CODD_CALIB_FISHEYE 1
+typedef struct codd_calib_view {
+  double R[9];
+  double f, cx, cy;
+  double K[4];
+  double dist[8];
+  int model;
+} codd_calib_view;
+int codd_rectify_maps(const codd_calib_view* left, const codd_calib_view* right, int h, int w, float* lmap_x,
+                      float* lmap_y, float* rmap_x, float* rmap_y, void* stream);
+int codd_ingest_calibrated(const unsigned char* left, const unsigned char* right, int fmt, int bgr, int yuv, int hs,
+                           int ws, long long pitch, const codd_calib_view* lcal, const codd_calib_view* rcal, int h,
+                           int w, const float* mean, const float* stdv, int H, int W, float* out_left,
+                           float* out_right, void* stream);
+
 /* Live-session export: the frame's padded disparity [1,1,H,W] -> the cropped h x w result, contiguous, in a
  * caller-owned device staging buffer (model/codd.py:370-377: `calib / pred_disp` under reciprocal, then the
  * [:img_h, :img_w] crop).  mode:
