@@ -1,7 +1,5 @@
-// The per-pixel decoders D_F of the raw camera formats (include/codd_hip.h: codd_ingest_frames) and the bilinear blend on
-// decoded taps, shared by the two ingest kernels that decode: ingest_frames_kernel (ingest_formats.hip, taps at map
-// entries) and ingest_calib_kernel (ingest_calib.hip, taps at the calibration map function evaluated in registers).
-// FrameArgs::h, w are always the size of the SOURCE frame: the decoders index the source with them.
+// The per-pixel decoders D_F of the source formats (include/codd_hip.h: codd_ingest_frames; CODD_FMT_RGB8 is the packed
+// 3-byte pixel of codd_ingest_pair) and the one bilinear blend on decoded taps, for ingest_kernel (ingest.hip).
 #pragma once
 #include "common.h"
 
@@ -10,16 +8,17 @@
 
 struct FrameArgs {
   const unsigned char* img[2];
-  const float* mx[2];
-  const float* my[2];
   float* out[2];
   long long pitch, bytes;  // bytes per source row; bytes of one view (codd_frame_bytes)
-  int h, w, H, W;
+  int h, w;                // the SOURCE frame: what the decoders index
+  int rh, rw;              // the rectified image: what the maps cover and the padding reflects (== h, w with map arrays)
+  int H, W;                // the padded output
+  int bgr;                 // the source channel order of CODD_FMT_RGB8
   int yoff, cy, cvr, cug, cvg, cub;  // the yuv row, coefficients in units of 2^-20
   float m0, m1, m2, s0, s1, s2;
 };
 
-#define FRAME_PX 4  // output pixels per thread, as INGEST_PX
+#define FRAME_PX 4  // output pixels per thread: one 16-byte store per channel row
 
 constexpr bool fmt_is_yuv422(int f) { return f == CODD_FMT_YUYV || f == CODD_FMT_UYVY; }
 constexpr bool fmt_is_bayer(int f) { return f >= CODD_FMT_BAYER_RGGB && f <= CODD_FMT_BAYER_BGGR; }
@@ -65,7 +64,7 @@ __device__ __forceinline__ int reflect101(int i, int n) {
 template <int FMT>
 __device__ __forceinline__ void frame_px(const FrameArgs& a, const unsigned char* __restrict__ img, int y, int x, int* c) {
   const long long p = a.pitch;
-  if (FMT == CODD_FMT_RGB8) {  // packed 3-byte pixels in source channel order (ingest_calib.hip only)
+  if (FMT == CODD_FMT_RGB8) {  // packed 3-byte pixels in source channel order
     const unsigned char* q = img + y * p + (long long)x * 3;
     c[0] = q[0]; c[1] = q[1]; c[2] = q[2];
   } else if (FMT == CODD_FMT_MONO8) {
@@ -161,8 +160,16 @@ __device__ __forceinline__ void frame_px4(const FrameArgs& a, const unsigned cha
   }
 }
 
-// raw (un-normalised) RGB of the source at position (sx, sy): ingest_sample's blend (live.hip), expression for
-// expression, on taps that are D_F at the integer source pixel, or 0 outside
+// THE BLEND of include/codd_hip.h in its stated fp32 operation order: every product that is not inside an fma rounds on
+// its own, so nothing is left for -ffp-contract to decide
+__device__ __forceinline__ float blend4(float v00, float v01, float v10, float v11, float ax, float ay) {
+  const float w0 = __fsub_rn(1.f, ax), w1 = __fsub_rn(1.f, ay);
+  const float top = __fmaf_rn(v00, w0, __fmul_rn(v01, ax)), bot = __fmaf_rn(v10, w0, __fmul_rn(v11, ax));
+  return __fmaf_rn(top, w1, __fmul_rn(bot, ay));
+}
+
+// raw (un-normalised) channels of the source at position (sx, sy): the blend of the four taps, each D_F at the integer
+// source pixel, or 0 outside
 template <int FMT>
 __device__ __forceinline__ void frame_blend(const FrameArgs& a, const unsigned char* __restrict__ img, float sx, float sy,
                                             float* c) {
@@ -207,9 +214,6 @@ __device__ __forceinline__ void frame_blend(const FrameArgs& a, const unsigned c
       }
   }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float v00 = (float)t[0][0][k], v01 = (float)t[0][1][k], v10 = (float)t[1][0][k], v11 = (float)t[1][1][k];
-    const float top = v00 * (1.f - ax) + v01 * ax, bot = v10 * (1.f - ax) + v11 * ax;
-    c[k] = top * (1.f - ay) + bot * ay;
-  }
+  for (int k = 0; k < 3; ++k)
+    c[k] = blend4((float)t[0][0][k], (float)t[0][1][k], (float)t[1][0][k], (float)t[1][1][k], ax, ay);
 }

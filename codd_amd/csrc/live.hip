@@ -1,136 +1,9 @@
-// Live-session kernels: the launches that bracket the captured frame graph when frames arrive one at a time from a
-// camera (codd_amd/live.py).  Ingest and depth export are pure streaming kernels: no LDS, several pixels per thread,
-// 16-byte stores, a scalar tail; the motion export moves 28-byte and 8- / 12-byte records and stages them in LDS.
-// All run on the compute stream outside the graph.
+// Live-session export kernels: the launches that follow the captured frame graph when frames arrive one at a time from a
+// camera (codd_amd/live.py); the ingest launch in front of it is ingest.hip.  The depth export is a pure streaming kernel:
+// no LDS, several pixels per thread, 16-byte stores, a scalar tail; the motion export moves 28-byte and 8- / 12-byte
+// records and stages them in LDS.  All run on the compute stream outside the graph.
 #include "common.h"
 #include "se3.h"
-
-// ------------------------------------------------------------------------------------------------
-// codd_ingest_pair: both views of one frame, uint8 HWC -> normalised reflect-padded fp32 CHW, optionally through a
-// rectifying bilinear remap (reference datasets/transforms.py:147-161 Pad, :373-427 Normalize,
-// datasets/formating.py:65-85, applied to img and r_img by datasets/custom_stereo_mf.py; the remap is the
-// cv2.remap(INTER_LINEAR, BORDER_CONSTANT 0) a user of the reference runs on the host before either).
-// ------------------------------------------------------------------------------------------------
-struct IngestArgs {
-  const unsigned char* img[2];
-  const float* mx[2];
-  const float* my[2];
-  float* out[2];
-  int h, w, H, W, bgr;
-  float m0, m1, m2, s0, s1, s2;
-};
-
-#define INGEST_PX 4  // output pixels per thread: one 16-byte store per channel row, 12 source bytes = 3 dwords
-
-// raw (un-normalised) channel values of rectified pixel (y, x) of the h x w image, in source channel order
-__device__ __forceinline__ void ingest_sample(const unsigned char* __restrict__ img, const float* __restrict__ mx,
-                                              const float* __restrict__ my, int h, int w, int y, int x, float* c) {
-  const size_t o = (size_t)y * w + x;
-  if (!mx) {
-    const unsigned char* p = img + o * 3;
-    c[0] = p[0]; c[1] = p[1]; c[2] = p[2];
-    return;
-  }
-  const float sx = mx[o], sy = my[o];
-  c[0] = c[1] = c[2] = 0.f;
-  // every tap outside (this also catches NaN and +-inf: the comparisons are false) -> 0
-  if (!(sx > -1.f && sx < (float)w && sy > -1.f && sy < (float)h)) return;
-  const float fx0 = floorf(sx), fy0 = floorf(sy);
-  const float ax = sx - fx0, ay = sy - fy0;
-  const int x0 = (int)fx0, y0 = (int)fy0;
-  const bool xin0 = x0 >= 0, xin1 = x0 + 1 < w, yin0 = y0 >= 0, yin1 = y0 + 1 < h;
-  const unsigned char* p00 = img + ((ptrdiff_t)y0 * w + x0) * 3;
-  const unsigned char* p10 = p00 + (ptrdiff_t)w * 3;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float v00 = (yin0 && xin0) ? (float)p00[k] : 0.f, v01 = (yin0 && xin1) ? (float)p00[3 + k] : 0.f;
-    const float v10 = (yin1 && xin0) ? (float)p10[k] : 0.f, v11 = (yin1 && xin1) ? (float)p10[3 + k] : 0.f;
-    const float top = v00 * (1.f - ax) + v01 * ax, bot = v10 * (1.f - ax) + v11 * ax;
-    c[k] = top * (1.f - ay) + bot * ay;
-  }
-}
-
-__global__ __launch_bounds__(256) void ingest_pair_kernel(IngestArgs a) {
-  const int v = blockIdx.y;
-  const unsigned char* __restrict__ img = a.img[v];
-  const float* __restrict__ mx = a.mx[v];
-  const float* __restrict__ my = a.my[v];
-  float* __restrict__ out = a.out[v];
-  const int h = a.h, w = a.w, H = a.H, W = a.W;
-  const int W4 = (W + INGEST_PX - 1) / INGEST_PX;
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (long long)H * W4) return;
-  const int y = (int)(t / W4), x4 = (int)(t - (long long)y * W4) * INGEST_PX;
-  const int sy = y < h ? y : 2 * (h - 1) - y;  // reflect without edge repeat (cv2.BORDER_REFLECT_101)
-  float c[INGEST_PX][3];
-  bool loaded = false;
-  if (!mx && x4 + INGEST_PX <= w && ((uintptr_t)img & 3) == 0) {
-    // map-free interior: the 12 bytes of 4 packed pixels as dwords.  A row start is dword-aligned only when
-    // sy * w is a multiple of 4, so read the aligned dwords around them and shift by the byte misalignment.
-    const size_t off = ((size_t)sy * w + x4) * 3, total = (size_t)h * w * 3;
-    const unsigned sh = (unsigned)(off & 3);
-    const size_t a0 = off - sh;
-    if (sh == 0 || a0 + 16 <= total) {  // (the 4th dword must lie inside the image)
-      const unsigned* q = (const unsigned*)(img + a0);
-      const unsigned d0 = q[0], d1 = q[1], d2 = q[2], d3 = sh ? q[3] : 0u;
-      const unsigned s8 = sh * 8;
-      const unsigned r0 = (unsigned)((((unsigned long long)d1 << 32) | d0) >> s8);
-      const unsigned r1 = (unsigned)((((unsigned long long)d2 << 32) | d1) >> s8);
-      const unsigned r2 = (unsigned)((((unsigned long long)d3 << 32) | d2) >> s8);
-      c[0][0] = (float)(r0 & 255u); c[0][1] = (float)((r0 >> 8) & 255u); c[0][2] = (float)((r0 >> 16) & 255u);
-      c[1][0] = (float)(r0 >> 24); c[1][1] = (float)(r1 & 255u); c[1][2] = (float)((r1 >> 8) & 255u);
-      c[2][0] = (float)((r1 >> 16) & 255u); c[2][1] = (float)(r1 >> 24); c[2][2] = (float)(r2 & 255u);
-      c[3][0] = (float)((r2 >> 8) & 255u); c[3][1] = (float)((r2 >> 16) & 255u); c[3][2] = (float)(r2 >> 24);
-      loaded = true;
-    }
-  }
-  if (!loaded) {
-#pragma unroll
-    for (int i = 0; i < INGEST_PX; ++i) {
-      const int x = x4 + i;
-      if (x < W) {
-        const int sx = x < w ? x : 2 * (w - 1) - x;
-        ingest_sample(img, mx, my, h, w, sy, sx, c[i]);
-      } else {
-        c[i][0] = c[i][1] = c[i][2] = 0.f;
-      }
-    }
-  }
-  const size_t N = (size_t)H * W, o = (size_t)y * W + x4;
-  const float m0 = a.m0, m1 = a.m1, m2 = a.m2, s0 = a.s0, s1 = a.s1, s2 = a.s2;
-  f32x4 r0, r1, r2;
-#pragma unroll
-  for (int i = 0; i < INGEST_PX; ++i) {
-    const float c0 = a.bgr ? c[i][2] : c[i][0], c1 = c[i][1], c2 = a.bgr ? c[i][0] : c[i][2];
-    r0[i] = (c0 - m0) / s0; r1[i] = (c1 - m1) / s1; r2[i] = (c2 - m2) / s2;  // preprocess_kernel's expression
-  }
-  if ((W & 3) == 0 && ((uintptr_t)out & 15) == 0) {  // (then x4 + 4 <= W and every row / plane offset is 16-byte aligned)
-    *(f32x4*)(out + o) = r0; *(f32x4*)(out + N + o) = r1; *(f32x4*)(out + 2 * N + o) = r2;
-  } else {
-#pragma unroll
-    for (int i = 0; i < INGEST_PX; ++i)
-      if (x4 + i < W) { out[o + i] = r0[i]; out[N + o + i] = r1[i]; out[2 * N + o + i] = r2[i]; }
-  }
-}
-
-extern "C" int codd_ingest_pair(const unsigned char* left, const unsigned char* right, int h, int w, int bgr,
-                                const float* mean, const float* stdv, const float* lmap_x, const float* lmap_y,
-                                const float* rmap_x, const float* rmap_y, int H, int W, float* out_left,
-                                float* out_right, void* stream) {
-  if (!left || !right || !mean || !stdv || !out_left || !out_right) return CODD_EINVAL;
-  if (h <= 0 || w <= 0 || H < h || W < w || H - h >= h || W - w >= w) return CODD_EINVAL;
-  if ((lmap_x == nullptr) != (lmap_y == nullptr) || (rmap_x == nullptr) != (rmap_y == nullptr)) return CODD_EINVAL;
-  IngestArgs a;
-  a.img[0] = left; a.img[1] = right;
-  a.mx[0] = lmap_x; a.my[0] = lmap_y; a.mx[1] = rmap_x; a.my[1] = rmap_y;
-  a.out[0] = out_left; a.out[1] = out_right;
-  a.h = h; a.w = w; a.H = H; a.W = W; a.bgr = bgr;
-  a.m0 = mean[0]; a.m1 = mean[1]; a.m2 = mean[2]; a.s0 = stdv[0]; a.s1 = stdv[1]; a.s2 = stdv[2];
-  const long long threads = (long long)H * cdiv(W, INGEST_PX);
-  ingest_pair_kernel<<<dim3(cdiv(threads, 256), 2), 256, 0, (hipStream_t)stream>>>(a);
-  CODD_LAUNCH_CHECK();
-  return CODD_OK;
-}
 
 // ------------------------------------------------------------------------------------------------
 // codd_export_depth: the frame's padded disparity -> the cropped result in the caller's staging buffer (reference

@@ -1726,6 +1726,23 @@ def preprocess(img_u8, bgr=True, mean=IMAGENET_MEAN, std=IMAGENET_STD, divisor=6
     return out
 
 
+def _ingest_args(left_u8, right_u8, out_left, out_right, src_ok, maps, map_shape, mean, std):
+    """What the ingest wrappers share: the asserts on the source views (``src_ok``: shape or size of one) and on the output
+    buffers, the four map pointers (None where a view has no maps) and the mean / std arrays -> (H, W, pointers, mean, std)."""
+    for t in (left_u8, right_u8):
+        assert t.dtype == torch.uint8 and src_ok(t) and t.is_contiguous() and t.is_cuda
+    H, W = out_left.shape[-2:]
+    for t in (out_left, out_right):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and t.numel() == 3 * H * W
+    ptrs = []
+    for pair in (maps or (None, None)):
+        for m in (pair or (None, None)):
+            if m is not None:
+                assert m.dtype == torch.float32 and tuple(m.shape) == tuple(map_shape) and m.is_contiguous() and m.is_cuda
+            ptrs.append(None if m is None else m.data_ptr())
+    return H, W, ptrs, (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+
+
 def ingest_pair(left_u8, right_u8, out_left, out_right, bgr=True, maps=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """Both views of one frame in one launch: uint8 [h,w,3] device images -> normalised, reflect-padded fp32 written
     into the caller's [..,3,H,W] buffers (nothing is allocated).  ``maps``: None or ((lmx, lmy), (rmx, rmy)), fp32
@@ -1734,18 +1751,8 @@ def ingest_pair(left_u8, right_u8, out_left, out_right, bgr=True, maps=None, mea
     lib = _abi.load()
     _require_gpu(left_u8)
     h, w = left_u8.shape[:2]
-    for t in (left_u8, right_u8):
-        assert t.dtype == torch.uint8 and tuple(t.shape) == (h, w, 3) and t.is_contiguous() and t.is_cuda
-    H, W = out_left.shape[-2:]
-    for t in (out_left, out_right):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and t.numel() == 3 * H * W
-    ptrs = []
-    for pair in (maps or (None, None)):
-        for m in (pair or (None, None)):
-            if m is not None:
-                assert m.dtype == torch.float32 and tuple(m.shape) == (h, w) and m.is_contiguous() and m.is_cuda
-            ptrs.append(None if m is None else m.data_ptr())
-    m, s = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    H, W, ptrs, m, s = _ingest_args(left_u8, right_u8, out_left, out_right, lambda t: tuple(t.shape) == (h, w, 3), maps, (h, w),
+                                    mean, std)
     _abi.check(lib.codd_ingest_pair(left_u8.data_ptr(), right_u8.data_ptr(), h, w, int(bgr), m, s, *ptrs, H, W,
                                     out_left.data_ptr(), out_right.data_ptr(), _stream()), "ingest_pair")
 
@@ -1778,18 +1785,7 @@ def ingest_frames(left_u8, right_u8, out_left, out_right, fmt, shape, yuv="bt601
     nbytes = frame_bytes(fmt, h, w, pitch)
     if yuv not in YUV_MATRICES:
         raise ValueError(f"yuv: one of {tuple(YUV_MATRICES)} expected, got {yuv!r}")
-    for t in (left_u8, right_u8):
-        assert t.dtype == torch.uint8 and t.numel() == nbytes and t.is_contiguous() and t.is_cuda
-    H, W = out_left.shape[-2:]
-    for t in (out_left, out_right):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and t.numel() == 3 * H * W
-    ptrs = []
-    for pair in (maps or (None, None)):
-        for m in (pair or (None, None)):
-            if m is not None:
-                assert m.dtype == torch.float32 and tuple(m.shape) == (h, w) and m.is_contiguous() and m.is_cuda
-            ptrs.append(None if m is None else m.data_ptr())
-    m, s = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    H, W, ptrs, m, s = _ingest_args(left_u8, right_u8, out_left, out_right, lambda t: t.numel() == nbytes, maps, (h, w), mean, std)
     _abi.check(lib.codd_ingest_frames(left_u8.data_ptr(), right_u8.data_ptr(), FRAME_FORMATS[fmt], YUV_MATRICES[yuv], h, w,
                                       int(pitch or 0), m, s, *ptrs, H, W, out_left.data_ptr(), out_right.data_ptr(),
                                       _stream()), "ingest_frames")
@@ -1866,12 +1862,7 @@ def ingest_calibrated(left_u8, right_u8, out_left, out_right, rect, fmt, src_sha
     else:
         nbytes = frame_bytes(fmt, hs, ws, pitch)
     views = calib_structs(rect)
-    for t in (left_u8, right_u8):
-        assert t.dtype == torch.uint8 and t.numel() == nbytes and t.is_contiguous() and t.is_cuda
-    H, W = out_left.shape[-2:]
-    for t in (out_left, out_right):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and t.numel() == 3 * H * W
-    m, s = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    H, W, _, m, s = _ingest_args(left_u8, right_u8, out_left, out_right, lambda t: t.numel() == nbytes, None, None, mean, std)
     _abi.check(lib.codd_ingest_calibrated(left_u8.data_ptr(), right_u8.data_ptr(), CALIB_FORMATS[fmt], int(bool(bgr)),
                                           YUV_MATRICES[yuv], hs, ws, int(pitch or 0),
                                           *(None if v is None else C.byref(v) for v in views), h, w, m, s, H, W,

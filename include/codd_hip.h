@@ -555,6 +555,13 @@ int codd_preprocess(const unsigned char* img, int h, int w, int bgr, const float
  *   x0 = floor(sx), y0 = floor(sy); weights ax = sx - x0, ay = sy - y0 computed in fp32;
  *   a tap outside the source contributes 0 in raw uint8 units; a non-finite map entry gives 0;
  *   v = (v00*(1-ax) + v01*ax)*(1-ay) + (v10*(1-ax) + v11*ax)*ay in fp32, NOT rounded back to uint8; then (v - mean)/std.
+ * THE BLEND.  The fp32 operation order of v, per channel, in every ingest entry and for every source format (fma = one
+ * fused multiply-add, every other operation rounded to nearest on its own; v00, v01 the taps of row y0 at x0, x0 + 1 and
+ * v10, v11 those of row y0 + 1, as floats):
+ *   w0 = 1 - ax;  w1 = 1 - ay
+ *   top = fma(v00, w0, v01 * ax);  bot = fma(v10, w0, v11 * ax)
+ *   v   = fma(top, w1, bot * ay)
+ * On maps whose entries are multiples of 1/64 pixel (and on the identity map) no operation rounds at all.
  * The padded border is the BORDER_REFLECT_101 reflection of the RECTIFIED image.  An identity map gives the bits of the
  * map-free path.  Same size rules as codd_preprocess: h <= H < 2h, w <= W < 2w. */
 int codd_ingest_pair(const unsigned char* left, const unsigned char* right, int h, int w, int bgr, const float* mean,

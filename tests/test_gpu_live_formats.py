@@ -180,15 +180,20 @@ def test_ingest_frames_with_quantised_maps_equals_ingest_pair(case):
 
 
 # ---- 3. unquantised maps against the fp64 restatement -----------------------------------------------------------------
-@pytest.mark.parametrize("fmt,yuv", FMT_YUV, ids=lambda v: str(v))
-def test_ingest_frames_smooth_map_matches_fp64_restatement(fmt, yuv):
-    (h, w), (H, W) = SMALL[2]
-    left, right = _pair(fmt, h, w)
+def _smooth_maps(h, w):
+    """An unquantised barrel distortion per view: the weights of the blend have full fp32 mantissas."""
     yy, xx = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
     cx, cy = (w - 1) / 2.0, (h - 1) / 2.0
     r2 = ((xx - cx) ** 2 + (yy - cy) ** 2) / (cx * cx + cy * cy)
     lm = ((xx + 3.3 * r2 * (xx - cx) / cx + 0.2137).astype(np.float32), (yy + 3.3 * r2 * (yy - cy) / cy - 0.3719).astype(np.float32))
-    rm = tuple(np.ascontiguousarray(m[::-1, ::-1]) for m in lm)
+    return lm, tuple(np.ascontiguousarray(m[::-1, ::-1]) for m in lm)
+
+
+@pytest.mark.parametrize("fmt,yuv", FMT_YUV, ids=lambda v: str(v))
+def test_ingest_frames_smooth_map_matches_fp64_restatement(fmt, yuv):
+    (h, w), (H, W) = SMALL[2]
+    left, right = _pair(fmt, h, w)
+    lm, rm = _smooth_maps(h, w)
     gl, gr = _ingest_raw(left, right, fmt, yuv, h, w, H, W, maps=(lm, rm))
     worst = 0.0
     for got, rgb, m in zip((gl, gr), _decoded(fmt, yuv, h, w), (lm, rm)):
@@ -196,6 +201,22 @@ def test_ingest_frames_smooth_map_matches_fp64_restatement(fmt, yuv):
         worst = max(worst, float(np.abs(got[0].cpu().numpy().astype(np.float64) - ref).max()))
     print(f"smooth-map ingest {fmt} {yuv} {h}x{w}: max |delta| = {worst:.3e} (bound {RECT_TOL:g})")
     assert worst <= RECT_TOL
+
+
+@pytest.mark.parametrize("fmt", fr.FORMATS)
+def test_ingest_frames_smooth_map_equals_ingest_pair_bit_for_bit(fmt):
+    """The blend has ONE fp32 operation order (include/codd_hip.h: THE BLEND) in every instantiation of the one ingest
+    kernel, so the contract "decode, then ingest_pair" holds to the bit on maps where the blend rounds, too."""
+    (h, w), (H, W) = SMALL[2]
+    left, right = _pair(fmt, h, w)
+    rl, rr = _decoded(fmt, "bt601", h, w)
+    maps = _smooth_maps(h, w)
+    frac = np.modf(maps[0][0] * 64.0)[0]
+    assert (frac != 0).mean() > 0.9, "the map must not be quantised"
+    wl, wr = _ingest_rgb(rl, rr, H, W, maps)
+    gl, gr = _ingest_raw(left, right, fmt, "bt601", h, w, H, W, maps=maps)
+    assert _same(gl, wl), "left view differs"
+    assert _same(gr, wr), "right view differs"
 
 
 # ---- 4. pitch ------------------------------------------------------------------------------------------------------------

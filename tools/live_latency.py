@@ -15,7 +15,7 @@ clock and thermal drift hit all of them alike:
 
 Raw camera formats (LiveSession(pixel_format=)): `--pixel-format all` adds one pipelined variant d:<format> per format, fed
 raw frames of the same images, and an upload-bytes column; the ingest kernel alone, every format map-free and rectified
-next to rgb8's ingest_pair_kernel (three times, for the spread), is timed per dispatch from a kernel trace:
+next to rgb8's ingest_kernel<0, ArrayMaps> (three times, for the spread), is timed per dispatch from a kernel trace:
 
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o t -- python tools/live_latency.py --pixel-format all --ingest-kernels 40
     python tools/live_latency.py --pixel-format all --ingest-kernels 40 --parse-trace DIR/t_kernel_trace.csv    # the table
@@ -73,6 +73,7 @@ def raw_of(rgb, fmt):
 
 
 INGEST_WARM = 5  # --ingest-kernels: untimed launches in front of every block
+INGEST_KERNEL = "ingest_kernel<"  # ingest_kernel<FMT, MAP> (ingest.hip); FMT 0 = rgb8
 
 
 def ingest_schedule(formats, n):
@@ -107,7 +108,7 @@ def parse_ingest_trace(path, formats, n):
     """The kernel trace (csv) of an --ingest-kernels run with the same --pixel-format and count -> the table."""
     import csv
     ev = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(open(path))
-                if "ingest_pair_kernel" in r["Kernel_Name"] or "ingest_frames_kernel" in r["Kernel_Name"])
+                if INGEST_KERNEL in r["Kernel_Name"])
     sched = ingest_schedule(formats, n)
     assert len(ev) == sum(b[2] for b in sched), f"{len(ev)} ingest dispatches in the trace, the schedule has {sum(b[2] for b in sched)}"
     from codd_amd.live import frame_layout
@@ -115,7 +116,7 @@ def parse_ingest_trace(path, formats, n):
     for fmt, cfg, launches in sched:
         us = np.array([(e - s) / 1e3 for s, e, _ in ev[i + INGEST_WARM:i + launches]])
         names = {k for _, _, k in ev[i:i + launches]}
-        assert len(names) == 1 and ("ingest_pair_kernel" in next(iter(names))) == (fmt == "rgb8"), (fmt, names)
+        assert len(names) == 1 and ((INGEST_KERNEL + "0,") in next(iter(names))) == (fmt == "rgb8"), (fmt, names)
         blocks.setdefault((fmt, cfg), []).append(float(np.median(us)))
         i += launches
     lines = ["| format | upload bytes / frame | map-free median us | rectified median us |", "|---|---|---|---|"]

@@ -1,13 +1,15 @@
 #!/usr/bin/env python
-"""dev (GPU box): write tests/golden/load_chain_bits.json -- sha256 of the output bytes of the launches of
-tests/load_chain_cases.py (instance norm, Gauss-Newton step, splat), produced by the library this process loads, with
-the commit that library was built from:
+"""dev (GPU box): write a parent-bits fixture tests/golden/<name>_bits.json -- sha256 of the output bytes of the launches
+of a case module tests/<name>_cases.py (its groups() / all_keys() / all_digests()), produced by the library this process
+loads, with the commit that library was built from:
 
     CODD_LIB_AB=ab/libcodd_hip_parent.so python tools/load_chain_bits.py --commit <id> --out /tmp/load_chain_bits.json
+    CODD_LIB_AB=ab/libcodd_hip_parent.so python tools/load_chain_bits.py --cases ingest_cases --commit <id>
 
-The fixture is made ONCE with the library of the commit BEFORE the loads of instnorm_stats / instnorm_apply /
-instnorm_apply_xs / se3_gn_solve / splat_gather were re-ordered; tests/test_gpu_load_chain_bits.py then holds the in-tree
-library to those bits.
+A fixture is made ONCE with the library of the commit BEFORE the change it fences: load_chain_cases (the default; instance
+norm, Gauss-Newton step, splat) before the loads of instnorm_stats / instnorm_apply / instnorm_apply_xs / se3_gn_solve /
+splat_gather were re-ordered, held by tests/test_gpu_load_chain_bits.py; ingest_cases (the live-session ingest entries
+and codd_rectify_maps) before the three ingest kernels became one, held by tests/test_gpu_ingest_bits.py.
     --stub   no GPU: enumerate the keys only (every digest "stub"); the key list must not depend on the library."""
 import argparse
 import json
@@ -21,10 +23,14 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--commit", required=True, help="commit id of the sources the loaded library was built from")
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "load_chain_bits.json"))
+    ap.add_argument("--cases", default="load_chain_cases", metavar="MODULE", help="case module under tests/ (<name>_cases)")
+    ap.add_argument("--out", default=None, help="default: tests/golden/<name>_bits.json")
     ap.add_argument("--stub", action="store_true")
     a = ap.parse_args()
-    import load_chain_cases as LC
+    import importlib
+    assert a.cases.endswith("_cases"), a.cases
+    LC = importlib.import_module(a.cases)
+    a.out = a.out or os.path.join(ROOT, "tests", "golden", a.cases[:-len("_cases")] + "_bits.json")
     if a.stub:
         digests = {k: "stub" for k in LC.all_keys()}
         lib = "stub"
