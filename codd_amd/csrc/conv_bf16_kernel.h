@@ -484,12 +484,12 @@ __global__ __launch_bounds__((PGW * CGW * KS + CONVB_NWP) * 64) void conv_bf16_k
     return;
   }
 #endif
-  if constexpr (OUTF == 1) {
-    // Split-record epilogue (the output IS the next convolution's input, codd_split_bf16 layout): the MFMA was issued
-    // weights-first, D[m = co 4g + r][n = pixel j], so a lane holds 4 consecutive CHANNELS of one pixel; lanes g and
-    // g ^ 1 (16 apart) own the two halves of a channel octet.  After bias + activation each lane splits its 4 values
-    // into (hi, lo) bf16, the pair swaps one half through ds_bpermute, the even lane stores the 16-byte HI record and
-    // the odd lane the LO record: 16 pixels j -> 256 contiguous bytes per (octet, plane).  No fp32 tensor is written.
+  // The record epilogue exists in two forms.  EPI_BATCH (below this one): the operand loads of a block's tiles in one
+  // memory round trip, on the instantiations that take it without losing occupancy or gaining scratch -- the 12-unit
+  // two-plane kernels, which run the update block's gate 2 and gate 3 (profiles/convb_epilogue_resources.txt has every
+  // instantiation both ways).  Everywhere else the tile-at-a-time walk stays.  Both compute the same bits.
+  constexpr bool EPI_BATCH = NPL == 2 && A == 3;
+  if constexpr (OUTF == 1 && !EPI_BATCH) {  // (the record layout is described at the batched form)
     const int orec = p.xso_hp * p.xso_wp;
     uint4* xo = (uint4*)p.xso + (size_t)b * NPL * p.xso_c8 * orec;
     const bool odd = g & 1;
@@ -583,9 +583,211 @@ __global__ __launch_bounds__((PGW * CGW * KS + CONVB_NWP) * 64) void conv_bf16_k
     }
     return;
   }
+  if constexpr (OUTF == 1) {
+    // Split-record epilogue (the output IS the next convolution's input, codd_split_bf16 layout): the MFMA was issued
+    // weights-first, D[m = co 4g + r][n = pixel j], so a lane holds 4 consecutive CHANNELS of one pixel; lanes g and
+    // g ^ 1 (16 apart) own the two halves of a channel octet.  After bias + activation each lane splits its 4 values
+    // into (hi, lo) bf16, the pair swaps one half through ds_bpermute, the even lane stores the 16-byte HI record and
+    // the odd lane the LO record: 16 pixels j -> 256 contiguous bytes per (octet, plane).  No fp32 tensor is written.
+    //
+    // Memory schedule.  A tile-at-a-time walk (bias load, wait, res1 load, wait, ..., store, next tile) pays one L2
+    // round trip per LOAD: the operand and output pointers are kernel arguments, a store may alias the next load, so
+    // the compiler keeps program order and every s_waitcnt vmcnt(0) also drains the previous tile's store.  Here
+    //   * the wave's B distinct bias quads (co0 depends on m, not on a) are loaded once, in front of the tile loop;
+    //   * the tiles are walked one channel block m at a time, and for the A tiles of a block every gate operand
+    //     (res1, res2, post) is requested BEFORE the block's first arithmetic and first store: one wait per block;
+    //   * every value then takes the operations of the tile-at-a-time walk in their order, so it keeps its bits.
+    // An operand load goes to the lane's own quad where the lane is live, else to a clamped quad inside the map whose
+    // value a select drops (never an added zero: -0 and NaN survive).  Aliasing contract (include/codd_hip.h): an
+    // operand may be the output itself element for element -- gate 3 runs with out = post -- and nothing else; a live
+    // lane reads exactly the quads it writes and all of a block's loads precede its stores, a dropped value may be
+    // another lane's old or new one.
+#pragma clang fp contract(off)  // two roundings stay two wherever the scheduler moves them; gate 3's blend spells its fmaf
+    // the lane's coordinates once more, from a thread index that is opaque to the optimiser: every predicate and address
+    // of the epilogue is formed here, behind the K loop, instead of being kept in registers across it
+    int te_ = threadIdx.x;
+    asm volatile("" : "+v"(te_));
+    const int g = (te_ & 63) >> 4, j = te_ & 15;
+    const int orec = p.xso_hp * p.xso_wp;
+    uint4* xo = (uint4*)p.xso + (size_t)b * NPL * p.xso_c8 * orec;
+    const bool odd = g & 1;
+    constexpr bool MPAR = KS == 2 && B % 2 == 0;  // k-split tile parity (a * B + m) & 1 is that of m: whole blocks
+    // A batch is the A = 3 tiles of a block.  A tile in flight takes about 22 registers (three operand quads, the value
+    // quad, addresses) out of the 16 (A + B) = 80 or 112 that the K loop's two fragment sets leave dead.
+    int oy[A], ox[A];
+    bool inb[A];
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+      const int u = pgi * A + a;
+      const int prow = u / k.xb;
+      oy[a] = ty * k.th + prow;
+      ox[a] = tx * k.tw + (u - prow * k.xb) * 16 + j;
+      inb[a] = u < k.pu && oy[a] < p.Hout && ox[a] < p.Wout;
+    }
+    f32x4 bv[B];  // bias quad of channel block m (co0 is a multiple of 4: 16-byte aligned)
+#pragma unroll
+    for (int m = 0; m < B; ++m) {
+      const int co0 = (cog * CGW * B + cgi * B + m) * 16 + 4 * g;
+      bv[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (p.bias && !(MPAR && (m & 1) != kpart)) {
+        if (co0 + 3 < k.cout_eff) bv[m] = *(const f32x4*)(p.bias + co0);
+        else
+#pragma unroll
+          for (int r = 0; r < 4; ++r) bv[m][r] = co0 + r < k.cout_eff ? p.bias[co0 + r] : 0.f;
+      }
+    }
+    // ConvGRU gate epilogues on channel-quad fp32 tensors: a lane's 4 channels of one pixel are ONE 16-byte access,
+    // 16 lanes j = 256 contiguous bytes.  The 16-channel tile (and with it every branch) is wave-uniform.
+    const int hw_ = p.Hout * p.Wout;
+    auto c4 = [&](const float* base, int ctot, int c, int pix_) {
+      return (f32x4*)(base + (((size_t)b * (ctot >> 2) + (c >> 2)) * hw_ + pix_) * 4);
+    };
+    int pix[A];  // the lane's pixel, clamped into the map (a lane outside it loads a valid quad and drops it)
+#pragma unroll
+    for (int a = 0; a < A; ++a)
+      pix[a] = (oy[a] < p.Hout ? oy[a] : p.Hout - 1) * p.Wout + (ox[a] < p.Wout ? ox[a] : p.Wout - 1);
+#pragma unroll
+    for (int m = 0; m < B; ++m) {
+      if (MPAR && (m & 1) != kpart) continue;  // the k-split partner's block
+      const int ctile = (cog * CGW * B + cgi * B + m) * 16;  // wave-uniform
+      const int co0 = ctile + 4 * g;                         // this lane's first channel
+      auto mine = [&](int a) { return KS == 1 || MPAR || ((a * B + m) & 1) == kpart; };  // (not the k-split partner's tile)
+      f32x4 v[A];
+#pragma unroll
+      for (int a = 0; a < A; ++a) {
+        v[a] = acc[a][m];
+        if (p.bias) v[a] += bv[m];
+      }
+      int rco = co0;  // first channel of the lane's record half
+      if (p.gate) {
+        if (ctile >= k.cout_eff) continue;  // (gates: cout_eff is a multiple of 16, convb_geometry) nothing is stored
+        bool live[A];
+#pragma unroll
+        for (int a = 0; a < A; ++a) live[a] = inb[a] && co0 < k.cout_eff;
+        if (p.gate == 1) {
+#pragma unroll
+          for (int a = 0; a < A; ++a)
+            if (mine(a) && live[a]) *c4(p.out, p.out_ctot, p.out_coff + co0, pix[a]) = v[a];
+          continue;
+        }
+        const int G = p.gate == 2 ? k.cout_eff / 3 : k.cout_eff;
+        if (p.gate == 2) {
+          const bool zr = ctile < 2 * G, rh = zr && ctile >= G;  // z | r * h tiles take res2, r * h tiles post
+          f32x4 r1[A], r2[A], po[A];
+#pragma unroll
+          for (int a = 0; a < A; ++a) {
+            if (!mine(a)) continue;
+            r1[a] = *c4(p.res1.ptr, p.res1.ctot, p.res1.coff + co0, pix[a]);
+            if (zr) r2[a] = *c4(p.res2.ptr, p.res2.ctot, p.res2.coff + co0, pix[a]);
+            if (rh) po[a] = *c4(p.post.ptr, p.post.ctot, p.post.coff + co0 - G, pix[a]);
+          }
+#pragma unroll
+          for (int a = 0; a < A; ++a) {
+            if (!mine(a)) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              float t = v[a][r];
+              t = live[a] ? t + r1[a][r] : t;
+              if (zr) t = live[a] ? t + r2[a][r] : t;
+              v[a][r] = t;
+            }
+          }
+          if (!zr) {  // q's input stream
+#pragma unroll
+            for (int a = 0; a < A; ++a)
+              if (mine(a) && live[a]) *c4(p.out, p.out_ctot, p.out_coff + co0 - G, pix[a]) = v[a];
+            continue;
+          }
+#pragma unroll
+          for (int a = 0; a < A; ++a)
+            if (mine(a)) v[a] = convb_act_slow(v[a], CODD_ACT_SIGMOID);
+          if (!rh) {  // z
+#pragma unroll
+            for (int a = 0; a < A; ++a)
+              if (mine(a) && live[a]) *c4(p.out, p.out_ctot, p.out_coff + co0, pix[a]) = v[a];
+            continue;
+          }
+          rco = co0 - G;  // r * h -> records
+#pragma unroll
+          for (int a = 0; a < A; ++a) {
+            if (!mine(a)) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[a][r] = live[a] ? v[a][r] * po[a][r] : v[a][r];
+          }
+        } else {
+          f32x4 qi[A], z[A], h[A];
+#pragma unroll
+          for (int a = 0; a < A; ++a) {
+            if (!mine(a)) continue;
+            qi[a] = *c4(p.res1.ptr, p.res1.ctot, p.res1.coff + G + co0, pix[a]);
+            z[a] = *c4(p.res1.ptr, p.res1.ctot, p.res1.coff + co0, pix[a]);
+            h[a] = *c4(p.post.ptr, p.post.ctot, p.post.coff + co0, pix[a]);
+          }
+#pragma unroll
+          for (int a = 0; a < A; ++a) {
+            if (!mine(a)) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[a][r] = live[a] ? v[a][r] + qi[a][r] : v[a][r];
+          }
+#pragma unroll
+          for (int a = 0; a < A; ++a)
+            if (mine(a)) v[a] = convb_act_slow(v[a], CODD_ACT_TANH);
+#pragma unroll
+          for (int a = 0; a < A; ++a) {
+            if (!mine(a)) continue;
+            // h' = (1 - z) h + z q.  Left to the compiler's contraction this expression came out, in every
+            // instantiation, as ONE fused multiply-add z q + [(1 - z) h] on the quad's channels 0 and 1 and as two
+            // products and a sum on channels 2 and 3; the hidden state carries those bits, so they are spelled here.
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const float zz = live[a] ? z[a][r] : 0.f, hh = live[a] ? h[a][r] : 0.f;
+              const float keep = (1.f - zz) * hh;
+              v[a][r] = r < 2 ? fmaf(zz, v[a][r], keep) : keep + zz * v[a][r];
+            }
+            if (live[a]) *c4(p.out, p.out_ctot, p.out_coff + co0, pix[a]) = v[a];
+          }
+        }
+      } else {
+#pragma unroll
+        for (int a = 0; a < A; ++a)
+          if (mine(a)) v[a] = convb_act(v[a], p.act, 1);  // (CODD_ACT_RELU_CH0 is a per-channel activation of fp32 outputs only)
+      }
+#pragma unroll
+      for (int a = 0; a < A; ++a) {
+        if (!mine(a)) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[a][r] = co0 + r < k.cout_eff ? v[a][r] : 0.f;  // channel padding of the octet stays 0
+        unsigned hi2[2], lo2[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          if constexpr (F16) {  // fp16 records: one plane, or hi | lo (xso_terms == terms: convb_geometry)
+            const _Float16 h0 = (_Float16)v[a][2 * q], h1 = (_Float16)v[a][2 * q + 1];
+            const _Float16 l0 = (_Float16)(v[a][2 * q] - (float)h0), l1 = (_Float16)(v[a][2 * q + 1] - (float)h1);
+            hi2[q] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
+            lo2[q] = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
+          } else {
+            const __bf16 h0 = (__bf16)v[a][2 * q], h1 = (__bf16)v[a][2 * q + 1];
+            const __bf16 l0 = (__bf16)(v[a][2 * q] - (float)h0), l1 = (__bf16)(v[a][2 * q + 1] - (float)h1);
+            hi2[q] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
+            lo2[q] = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
+          }
+        }
+        // even lane needs the partner's hi, odd lane the partner's lo
+        const unsigned s0 = odd ? hi2[0] : lo2[0], s1 = odd ? hi2[1] : lo2[1];
+        const unsigned r0 = __shfl_xor(s0, 16, 64), r1 = __shfl_xor(s1, 16, 64);
+        const uint4 rec = odd ? make_uint4(r0, r1, lo2[0], lo2[1]) : make_uint4(hi2[0], hi2[1], r0, r1);
+        const int oct = (rco >> 3) + p.xso_o8;  // both lanes of the pair: same octet (co0 differs by 4)
+        if (inb[a] && (co0 & ~7) < k.cout_eff && (!odd || NPL == 2))
+          xo[(size_t)(odd ? p.xso_c8 * orec : 0) + ((size_t)oct * p.xso_hp + oy[a] + p.xso_bt) * p.xso_wp + ox[a] + p.xso_bl] = rec;
+      }
+    }
+    return;
+  }
   // epilogue.  The MFMA is issued with the im2col fragment as its first operand, so D[m = pixel 4g + r][n = co j]:
   // a lane holds FOUR CONSECUTIVE PIXELS of one output channel -- bias is one value per tile, residual / output
   // accesses are 16-byte vectors (4x fewer memory instructions than a channel-major accumulator layout)
+  // (this epilogue is the tile-at-a-time walk: batching its operand loads the way the record epilogue does cost every
+  // instantiation registers -- profiles/convb_epilogue_resources.txt -- and none of the update block's launches ends here)
   const int hwout = p.Hout * p.Wout;
   const bool vec = (p.Wout & 3) == 0 && p.store_mode == 0;
 #pragma unroll

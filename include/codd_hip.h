@@ -173,7 +173,11 @@ typedef struct {
    *        co in [2G, 3G): out_c4[co - G] = s                                                        (q's input stream)
    *   3  Cout = G:   q = tanh(acc + bias + res1_c4[G + co]),  z = res1_c4[co],  h = post_c4[co]:
    *        h' = (1 - z) h + z q  ->  out_c4[co] (may be the post tensor: in place) and xso[co] (records)
-   * (reference blocks/gru.py:17-34 with the gate inputs summed by the producer, raft3d.py:92-106). */
+   * (reference blocks/gru.py:17-34 with the gate inputs summed by the producer, raft3d.py:92-106).
+   * Aliasing: the contract above holds for the gate operands too.  res1 / res2 / post may be the c4 tensor `out` itself
+   * element for element (same buffer, ctot and coff: gate 3 with out = post) and nothing else: the kernel requests the
+   * operand quads of several tiles before it stores the first of them (conv_bf16_kernel.h), a lane reads exactly the
+   * quads it writes, and a lane outside the map may read -- and drop -- a quad another lane is writing. */
   int gate;
 } codd_conv_params;
 
