@@ -1,7 +1,8 @@
 """The launches whose output bits tests/golden/conv_epilogue_vec_bits.json records (sha256 of the fp32 output bytes), shared
-by the generator tools/conv_epilogue_vec_bits.py and by tests/test_gpu_conv_epilogue_vec_bits.py.  They reach the decisions
-of the vector epilogue (conv_kernel.h conv_epilogue: a lane holds four consecutive pixels of one channel; 16-byte accesses
-where ConvK.evec allows, 4-byte accesses under a per-pixel predicate elsewhere) that tests/conv_epilogue_cases.py does not:
+by the generator tools/parent_bits.py --cases conv_epilogue_vec and by tests/test_gpu_conv_epilogue_vec_bits.py.  They
+reach the decisions of the vector epilogue (conv_kernel.h conv_epilogue: a lane holds four consecutive pixels of one
+channel; 16-byte accesses where ConvK.evec allows, 4-byte accesses under a per-pixel predicate elsewhere) that
+tests/conv_epilogue_cases.py does not:
 
 * ``vec/<layer>/<H>x<W>/n<npb>w<nw>/l<layout>``: five hand-made layers (the four of conv_epilogue_cases.HAND and one without
   a bias) at B = 2 on seven output sizes and seven launch configurations:
@@ -18,13 +19,14 @@ where ConvK.evec allows, 4-byte accesses under a per-pixel predicate elsewhere) 
   is per job.
 The recorded bits are those of the library BEFORE the MFMA operands were swapped and the epilogue rewritten: every output
 element is still C + sum_k w x over the same k in the same order and ((acc + bias) + res1) + res2 -> act -> + post."""
-import warnings
-
 import torch
 
 import conv_epilogue_cases as E
-from conv_epilogue_cases import DEV, SENTINEL, digest  # noqa: F401
+from conv_epilogue_cases import SENTINEL
+from parent_bits import DEV, digest, forced  # noqa: F401
 
+NAME = "conv_epilogue_vec"
+SOURCES = E.SOURCES
 B = E.V.B
 SIZES = ((9, 20), (5, 4), (9, 12), (6, 36), (9, 22), (9, 21), (7, 30))
 CONFIGS = ((1, 4, 0), (1, 4, 1), (2, 4, 0), (2, 4, 1), (4, 4, 0), (4, 4, 1), (1, 9, 1))  # (npb, nw, layout)
@@ -34,16 +36,8 @@ NO_BIAS = ("no_bias",)
 
 
 def geometry(name, H, W, layout):
-    """(Hin, Win, (pad t, l, b, r)) or None where the quad kernel cannot run the case (its input rows are a multiple of 4
-    floats)."""
-    k, deconv = LAYERS[name][2], LAYERS[name][4]
-    if deconv:
-        return None if (layout == 1 and W % 4) else (H, W, (0, 0, 0, 0))
-    assert k == 3
-    if layout == 1 and W % 4:
-        Win = W - W % 4
-        return (H, Win, (1, 1, 1, W + 1 - Win))
-    return (H, W, (1, 1, 1, 1))
+    """(Hin, Win, (pad t, l, b, r)) or None where the quad kernel cannot run the case (conv_epilogue_cases.geometry)."""
+    return E.geometry(LAYERS[name], H, W, layout)
 
 
 def key_of(name, H, W, npb, nw, layout):
@@ -56,92 +50,10 @@ def cases():
             for (npb, nw, layout) in CONFIGS if geometry(name, H, W, layout) is not None]
 
 
-def _inputs(name, H, W, layout):
-    cin, cout, k, C1, deconv, act, operands = LAYERS[name]
-    Hin, Win, pad = geometry(name, H, W, layout)
-    g = torch.Generator().manual_seed(11 + 1000 * list(LAYERS).index(name) + 10 * W + H + 7 * layout)
-    up = 2 if deconv else 1
-    d = dict(x=torch.randn(B, cin, Hin, Win, generator=g),
-             w=(torch.randn(cin, cout, 2, 2, generator=g) if deconv else torch.randn(cout, cin, k, k, generator=g)) / (cin * k * k) ** 0.5,
-             bias=None if name in NO_BIAS else torch.randn(cout, generator=g))
-    for o in ("res1", "res2", "post"):
-        d[o] = torch.randn(B, cout, H * up, W * up, generator=g) if o in operands else None
-    return d, (Hin, Win, pad)
-
-
-def _guarded(shape, fill, off):
-    """A contiguous tensor of ``shape`` that starts ``off`` floats into a flat sentinel-filled allocation (off = 1: 4
-    bytes past a 16-byte boundary), and the allocation."""
-    n = 1
-    for s in shape:
-        n *= s
-    flat = torch.full((n + 8,), SENTINEL, device=DEV)
-    t = flat[off:off + n].view(shape)
-    assert t.is_contiguous() and flat.data_ptr() % 16 == 0 and t.data_ptr() % 16 == 4 * off
-    t.fill_(fill)
-    return t, flat
-
-
 def launch(name, H, W, npb, nw, layout, in_place=False, misalign=False):
-    """One launch on the configuration (npb, nw, ck 16, mb, layout) -> the output on the host.  The first input is a Slice
-    of a sentinel-filled buffer, the output a Slice at channel 3 of a sentinel-filled buffer pre-filled with NaN; the
-    buffer's other channels must come back untouched.  ``in_place``: res1 IS the output Slice (pre-filled with res1's
-    values).  ``misalign``: the output buffer, res1 and post each start one float into a flat sentinel-filled allocation
-    (4 bytes off a 16-byte boundary; the input stays aligned); the floats in front of and behind each of them must come
-    back untouched, and res1 and post unchanged.  (The views are dense NCHW, as the library requires: between two channel
-    planes of a view there is no room for a sentinel, so what surrounds the planes is guarded -- the floats around every
-    allocation and the sentinel channels on both sides of the output Slice in every batch item -- and a write that leaves
-    its plane inside the Slice shows in the bit comparison with the aligned launch.)"""
-    from codd_amd import ops
-    from codd_amd.ops import Slice
-    cin, cout, k, C1, deconv, act, operands = LAYERS[name]
-    d, (Hin, Win, pad) = _inputs(name, H, W, layout)
-    C0, up = cin - C1, 2 if deconv else 1
-    off = 1 if misalign else 0
-    xbuf = torch.full((B, C0 + 8, Hin, Win), SENTINEL, device=DEV)
-    xbuf[:, 6:6 + C0] = d["x"][:, :C0].to(DEV)
-    x2 = d["x"][:, C0:].contiguous().to(DEV) if C1 else None
-    pc = ops.PackedConv(d["w"].to(DEV), None if d["bias"] is None else d["bias"].to(DEV), deconv=deconv)
-    obuf, oflat = _guarded((B, cout + 5, H * up, W * up), SENTINEL, off)
-    obuf[:, 3:3 + cout] = float("nan")
-    out = Slice(obuf, 3, cout)
-    guards = [(oflat, off)]
-    opnd = {}
-    for o in ("res1", "res2", "post"):
-        opnd[o] = None
-        if d[o] is not None:
-            o_off = off if o in ("res1", "post") else 0
-            t, flat = _guarded(tuple(d[o].shape), 0.0, o_off)
-            t.copy_(d[o].to(DEV))
-            opnd[o] = t
-            guards.append((flat, o_off))
-    if in_place:
-        assert opnd["res1"] is not None
-        obuf[:, 3:3 + cout] = opnd["res1"]
-        opnd["res1"] = out
-    cfg = (npb, nw, 16, pc.mb, layout)
-    key = (H, W, B, 1, 1, 1, 1, pad[1], C1 > 0, 0)
-    prev = ops.set_conv_precision("fp32")
-    try:
-        pc.tuned[key] = cfg
-        with warnings.catch_warnings(record=True) as caught:
-            warnings.simplefilter("always")
-            ops.conv2d(Slice(xbuf, 6, C0), pc, x2=x2, pad_tl=pad, act=act, res1=opnd["res1"], res2=opnd["res2"], post=opnd["post"],
-                       out=out, out_hw=None if deconv else (H, W))
-        torch.cuda.synchronize()
-    finally:
-        ops.set_conv_precision(prev)
-    assert dict(pc.tuned) == {key: cfg} and not caught, (dict(pc.tuned), [str(w.message) for w in caught])
-    host = obuf.cpu()
-    assert bool((host[:, :3] == SENTINEL).all()) and bool((host[:, 3 + cout:] == SENTINEL).all()), "sentinel channels"
-    for flat, g_off in guards:
-        f = flat.cpu()
-        n = f.numel() - 8
-        assert bool((f[:g_off] == SENTINEL).all()) and bool((f[g_off + n:] == SENTINEL).all()), "sentinel floats around an allocation"
-    for o in ("res1", "res2", "post"):
-        if isinstance(opnd[o], torch.Tensor):
-            assert torch.equal(opnd[o].cpu().view(torch.int32), d[o].view(torch.int32)), "operand %s changed" % o
-    return host[:, 3:3 + cout].contiguous()
+    """conv_epilogue_cases.launch of a layer of LAYERS -> the output on the host."""
+    return E.launch(LAYERS[name], H, W, npb, nw, layout, 11 + 1000 * list(LAYERS).index(name) + 10 * W + H + 7 * layout,
+                    bias=name not in NO_BIAS, in_place=in_place, misalign=misalign)
 
 
 def case_digests():
@@ -182,8 +94,9 @@ def multi_launch():
                 obuf = torch.full((B, 16 + 5, H, W), SENTINEL, device=DEV)
                 obuf[:, 3:3 + 16] = float("nan")
                 bufs.append(obuf)
-                j["pc"].tuned[(H, W, B, j["stride"], j["stride"], 1, 1, 1, False, 0)] = (1, 4, 16, 1, 1)
-                ops.conv2d(j["x"], j["pc"], stride=j["stride"], pad=1, act=j["act"], res1=j["res1"], out=Slice(obuf, 3, 16))
+                forced(j["pc"], (H, W, B, j["stride"], j["stride"], 1, 1, 1, False, 0), (1, 4, 16, 1, 1),
+                       lambda: ops.conv2d(j["x"], j["pc"], stride=j["stride"], pad=1, act=j["act"], res1=j["res1"],
+                                          out=Slice(obuf, 3, 16)))
         torch.cuda.synchronize()
     finally:
         ops._launch_conv_multi = real
@@ -202,5 +115,6 @@ def multi_digests():
     return {k: digest(o) for k, o in zip(multi_keys(), multi_launch())}
 
 
-def all_keys():
-    return [c[0] for c in cases()] + multi_keys()
+def groups():
+    """[(group id, keys, function -> {key: digest})] in the fixture's order."""
+    return [("cases", [c[0] for c in cases()], case_digests), ("multi", multi_keys(), multi_digests)]

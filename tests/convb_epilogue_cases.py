@@ -1,6 +1,6 @@
 """The launches whose output bits tests/golden/convb_epilogue_bits.json records (sha256 of the bytes the launch wrote),
-shared by the generator tools/convb_epilogue_bits.py and by tests/test_gpu_convb_epilogue_bits.py: the epilogues of the
-split-bf16 convolution kernel (conv_bf16_kernel.h) on every instantiated wave grid X(PGW, CGW, A, B, KS) of CONVB_ALL, in
+shared by the generator tools/parent_bits.py --cases convb_epilogue and by tests/test_gpu_convb_epilogue_bits.py: the
+epilogues of the split-bf16 convolution kernel (conv_bf16_kernel.h) on every instantiated wave grid X(PGW, CGW, A, B, KS) of CONVB_ALL, in
 the four operand formats (terms 1, 3, 16, 48), at B = 2 on three maps:
 
     9 x 21   partial tiles in both axes; the second 16-pixel unit of a row is valid for 5 lanes
@@ -22,12 +22,13 @@ room in the ring), tiles 32 pixels wide and PGW * A / 2 rows high.  Key ``<X>/<H
 Hazards: every operand and the bias hold one NaN and one -0.
 ``bias_off4`` (no digest): a bias 4 bytes off a 16-byte boundary must be refused with CODD_EINVAL."""
 import functools
-import hashlib
-import warnings
 
 import torch
 
-DEV = "cuda"
+from parent_bits import DEV, digest, forced
+
+NAME = "convb_epilogue"
+SOURCES = ("codd_amd/csrc/conv_bf16_kernel.h",)
 B = 2
 CIN = 32
 SENTINEL = 12345.0
@@ -73,10 +74,6 @@ def cases():
     return [(key_of(X, H, W, t, n), X, H, W, t, n) for X in CONVB_ALL for (H, W) in SIZES for t in TERMS for n in case_names(X)]
 
 
-def all_keys():
-    return [c[0] for c in cases()]
-
-
 def _hazards(t):
     """One NaN and one -0 in a tensor (first batch item, away from the corner)."""
     flat = t.view(-1)
@@ -106,13 +103,6 @@ def inputs(H, W):
     return d
 
 
-def digest(*tensors):
-    h = hashlib.sha256()
-    for t in tensors:
-        h.update(t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes())
-    return h.hexdigest()
-
-
 def _record_tensor(C, H, W, border, coff, terms):
     """A zeroed SplitTensor as ops.split_buffer makes them, with room for C channels from channel ``coff`` on; the image
     interior of the octets the launch writes is pre-filled with 0x5A bytes."""
@@ -137,17 +127,6 @@ def _c4(t, pad=0):
     return ops.to_c4(full.to(DEV), c4)
 
 
-def _forced(pc, key, cfg, fn):
-    """Run ``fn`` with ``pc`` pinned to the stored configuration ``cfg`` under ``key``; no fallback may happen."""
-    pc.tuned.clear()
-    pc.tuned[key] = tuple(cfg)
-    with warnings.catch_warnings(record=True) as caught:
-        warnings.simplefilter("always")
-        fn()
-    torch.cuda.synchronize()
-    assert dict(pc.tuned) == {key: tuple(cfg)} and not caught, (dict(pc.tuned), key, cfg, [str(w.message) for w in caught])
-
-
 def launch(X, H, W, terms, name, bias_off4=False):
     """One launch of instantiation X -> the digest of what it wrote."""
     from codd_amd import ops
@@ -166,7 +145,7 @@ def launch(X, H, W, terms, name, bias_off4=False):
                 assert pc.bias.data_ptr() % 16 == 4
             rec = _record_tensor(cout, H, W, border, coff, terms)
             key = (H, W, B, 1, 1, 1, 1, 1, False, terms, "split")
-            _forced(pc, key, cfg, lambda: ops.conv2d(d["x"].to(DEV), pc, pad=1, act=act, xs_out=rec, xs_out_coff=coff))
+            forced(pc, key, cfg, lambda: ops.conv2d(d["x"].to(DEV), pc, pad=1, act=act, xs_out=rec, xs_out_coff=coff))
             return digest(rec.buf)
         if name in GATES:
             gate = int(name[1])
@@ -177,22 +156,22 @@ def launch(X, H, W, terms, name, bias_off4=False):
             key = ("gate", gate, H, W, B, 1, 1, 0, terms)
             if gate == 1:
                 out = _c4(torch.full((B, cout, H, W), float("nan")), 4)
-                _forced(pc, key, cfg, lambda: ops.conv_gate(pc, xs, 1, pad=1, out=out, out_coff=4))
+                forced(pc, key, cfg, lambda: ops.conv_gate(pc, xs, 1, pad=1, out=out, out_coff=4))
                 return digest(out.buf)
             rec = _record_tensor(G, H, W, 1, 0, terms)
             if gate == 2:
                 out = _c4(torch.full((B, 2 * G, H, W), float("nan")), 4)
                 ctx, t12, h = _c4(d["res1", 3 * G]), _c4(d["res2", 2 * G]), _c4(d["h", G])
-                _forced(pc, key, cfg, lambda: ops.conv_gate(pc, xs, 2, pad=1, out=out, out_coff=4, res1=ctx, res2=t12, post=h,
+                forced(pc, key, cfg, lambda: ops.conv_gate(pc, xs, 2, pad=1, out=out, out_coff=4, res1=ctx, res2=t12, post=h,
                                                             xs_out=rec))
                 assert digest(ctx.buf, t12.buf, h.buf) == digest(_c4(d["res1", 3 * G]).buf, _c4(d["res2", 2 * G]).buf, _c4(d["h", G]).buf), "operand changed"
                 return digest(out.buf, rec.buf)
             zq, h = _c4(d["zq", 2 * G]), _c4(d["h", G])
             if name == "g3_inplace":
-                _forced(pc, key, cfg, lambda: ops.conv_gate(pc, xs, 3, pad=1, out=h, res1=zq, post=h, xs_out=rec))
+                forced(pc, key, cfg, lambda: ops.conv_gate(pc, xs, 3, pad=1, out=h, res1=zq, post=h, xs_out=rec))
                 return digest(h.buf, rec.buf)
             out = _c4(torch.full((B, G, H, W), float("nan")), 4)
-            _forced(pc, key, cfg, lambda: ops.conv_gate(pc, xs, 3, pad=1, out=out, out_coff=4, res1=zq, post=h, xs_out=rec))
+            forced(pc, key, cfg, lambda: ops.conv_gate(pc, xs, 3, pad=1, out=out, out_coff=4, res1=zq, post=h, xs_out=rec))
             host = out.nchw().cpu()
             assert bool((host[:, :4] == SENTINEL).all()) and bool((host[:, 4 + G:] == SENTINEL).all()), "sentinel channels"
             return digest(host[:, 4:4 + G], rec.buf)
@@ -210,7 +189,7 @@ def launch(X, H, W, terms, name, bias_off4=False):
             opnd["res1"] = out
         pad = 0 if deconv else 1
         key = (H, W, B, 1, 1, 1, 1, pad, False, terms)
-        _forced(pc, key, cfg, lambda: ops.conv2d(d["x"].to(DEV), pc, pad=pad, act="none" if deconv else "relu_ch0", out=out, **opnd))
+        forced(pc, key, cfg, lambda: ops.conv2d(d["x"].to(DEV), pc, pad=pad, act="none" if deconv else "relu_ch0", out=out, **opnd))
         host = obuf.cpu()
         assert bool((host[:, :3] == SENTINEL).all()) and bool((host[:, 3 + cout:] == SENTINEL).all()), "sentinel channels"
         return digest(host[:, 3:3 + cout])
@@ -218,5 +197,15 @@ def launch(X, H, W, terms, name, bias_off4=False):
         ops.set_conv_precision(prev)
 
 
-def case_digests(only=None):
-    return {key: launch(*rest) for (key, *rest) in cases() if only is None or only(key)}
+def case_digests(mine):
+    """``mine``: entries of cases()."""
+    return {key: launch(*rest) for (key, *rest) in mine}
+
+
+def groups():
+    """[(group id, keys, function -> {key: digest})] in the fixture's order: one group per instantiation X.  (The fixture
+    lists an instantiation's maps outside its operand formats, so the (X, terms) unit of the test is no contiguous run
+    of keys and cannot be a group.)"""
+    every = cases()
+    by_x = [(X, [c for c in every if c[1] == X]) for X in CONVB_ALL]
+    return [(xname(X), [c[0] for c in mine], functools.partial(case_digests, mine)) for (X, mine) in by_x]

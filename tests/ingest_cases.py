@@ -1,5 +1,5 @@
 """The live-ingest launches whose output bits tests/golden/ingest_bits.json records (sha256 of the bytes of one output
-view), shared by the generator tools/load_chain_bits.py --cases ingest_cases, by tests/test_gpu_ingest_bits.py and by
+view), shared by the generator tools/parent_bits.py --cases ingest, by tests/test_gpu_ingest_bits.py and by
 tests/test_ingest_cases.py.  The recorded bits are those of the library BEFORE the three ingest kernels became one and
 the bilinear blend got a pinned operation order.  Every case here is EXACT -- no map, an identity map, or a 1/64-pixel
 map, on which every intermediate of the blend is a short dyadic number -- so any correct evaluation order gives the same
@@ -18,7 +18,6 @@ is the left's turned by 180 degrees); ``left`` / ``right``: only that view has t
   takes the map-free path and is the one digested (the calibrated view blends at unquantised positions: not exact).
 * ``maps/<model>/<h>x<w>/<view>``: ops.rectify_maps, both maps of the view; 37 x 53 takes the scalar stores."""
 import functools
-import hashlib
 import zlib
 
 import numpy as np
@@ -26,8 +25,12 @@ import torch
 
 import live_calib_ref as cr
 import live_fmt_ref as fr
+from parent_bits import DEV, digest
 
-DEV = "cuda:0"
+NAME = "ingest"
+# the sources of the ingest entries, in the tree of the fixture's commit and in this one
+SOURCES = ("codd_amd/csrc/live.hip", "codd_amd/csrc/ingest_decode.h", "codd_amd/csrc/ingest_formats.hip",
+           "codd_amd/csrc/ingest_calib.hip", "codd_amd/csrc/ingest.hip")
 IMAGE = (38, 54)
 OUTPUTS = ((64, 64), (40, 55))
 VIEWS = ("left", "right")
@@ -37,11 +40,6 @@ FRAME_FORMATS = tuple((f, "bt601") for f in fr.FORMATS) + (("nv12", "bt709"), ("
 CALIB_FORMATS = (("rgb8", False), ("rgb8", True)) + tuple((f, False) for f in fr.FORMATS)
 MODELS = ("brown", "fisheye")
 MAP_SHAPES = ((38, 54), (37, 53))
-
-
-def digest(t):
-    """sha256 over the bytes of a device tensor (NaN payloads included)."""
-    return hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()
 
 
 def size_id(HW):
@@ -210,16 +208,3 @@ def groups():
                 ("frames/" + size_id(HW), frames_keys(HW), functools.partial(frames_digests, HW)),
                 ("calib/" + size_id(HW), calib_keys(HW), functools.partial(calib_digests, HW))]
     return out + [("maps/" + m, maps_keys(m), functools.partial(maps_digests, m)) for m in MODELS]
-
-
-def all_keys():
-    return [k for (_, keys, _) in groups() for k in keys]
-
-
-def all_digests():
-    out = {}
-    for (_, keys, fn) in groups():
-        got = fn()
-        assert list(got) == keys
-        out.update(got)
-    return out

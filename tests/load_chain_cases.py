@@ -1,5 +1,5 @@
 """The launches whose output bits tests/golden/load_chain_bits.json records (sha256 of the output bytes), shared by the
-generator tools/load_chain_bits.py, by tests/test_gpu_load_chain_bits.py and by tests/test_load_chain_cases.py.  They cover
+generator tools/parent_bits.py --cases load_chain, by tests/test_gpu_load_chain_bits.py and by tests/test_load_chain_cases.py.  They cover
 the five kernels of motion.hip whose loads were re-ordered (instnorm_stats / instnorm_apply / instnorm_apply_xs,
 se3_gn_solve, splat_gather); the recorded bits are those of the library BEFORE the re-ordering: no floating-point operation,
 operand or order changed, so every output byte stays.
@@ -23,26 +23,17 @@ operand or order changed, so every output byte stays.
   radius 4 under a sideways translation that leaves a band of pixels without a candidate.  featA[:, 0, 0, 0] is NaN: slot
   values of empty slots are read from pixel 0 and must not reach the sum."""
 import functools
-import hashlib
 
 import numpy as np
 import torch
 
 import motion_fp64 as M
+from parent_bits import DEV, digest
 
-DEV = "cuda:0"
+NAME = "load_chain"
+SOURCES = ("codd_amd/csrc/motion.hip",)
 STATS_DEPTH = 8  # IN_STATS_DEPTH of motion.hip
 SOLVE_BATCH = 16  # GN_SOLVE_BATCH of motion.hip
-
-
-def digest(*tensors):
-    """sha256 over the bytes of host tensors (NaN payloads included), in order."""
-    h = hashlib.sha256()
-    for t in tensors:
-        t = t.contiguous()
-        assert t.device.type == "cpu"
-        h.update(t.numpy().tobytes())
-    return h.hexdigest()
 
 
 # ------------------------------------------------------------------------------------------------ instance norm
@@ -269,16 +260,3 @@ def groups():
     return ([("inorm/" + inorm_id(s), inorm_keys(s), functools.partial(inorm_digests, s)) for s in INORM_SHAPES + INORM_PLANTED] +
             [("gn/" + gn_id(c), gn_keys(c), functools.partial(gn_digests, c)) for c in GN_CASES] +
             [("splat/" + n, splat_keys(n), functools.partial(splat_digests, n)) for n in SPLAT_GEOMETRIES])
-
-
-def all_keys():
-    return [k for (_, keys, _) in groups() for k in keys]
-
-
-def all_digests():
-    out = {}
-    for (_, keys, fn) in groups():
-        got = fn()
-        assert list(got) == keys
-        out.update(got)
-    return out

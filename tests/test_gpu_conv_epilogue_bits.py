@@ -1,6 +1,6 @@
 """The exact-fp32 convolution kernels (conv_kernel.h, conv_quad_kernel.h) reproduce, bit for bit, the outputs that the
 library of an EARLIER commit produced: tests/golden/conv_epilogue_bits.json holds sha256 of the output bytes per launch
-(tools/conv_epilogue_bits.py wrote it on the GPU with that library; the launches: tests/conv_epilogue_cases.py).  The
+(tools/parent_bits.py wrote it on the GPU with that library; the launches: tests/conv_epilogue_cases.py).  The
 batched epilogue (conv_epilogue) only moves loads ahead of stores, so not one rounding may change:
 
 * every exact-fp32 entry of the shipped-configuration sweep (launched as tests/test_gpu_conv_fp64.py::_launch does);
@@ -9,56 +9,34 @@ batched epilogue (conv_epilogue) only moves loads ahead of stores, so not one ro
   transposed-convolution store, res1 + res2 + post with relu_ch0;
 * in place: res1 IS the output Slice (the aliasing contract of include/codd_hip.h) -- the bits of the out-of-place launch.
 A key missing from the fixture, or one the fixture has and the tree does not, fails."""
-import json
-import os
-import re
-import subprocess
-
 import pytest
 
 import conv_epilogue_cases as E
+import parent_bits as P
 import test_gpu_conv_fp64 as T
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURE = json.load(open(os.path.join(ROOT, "tests", "golden", "conv_epilogue_bits.json")))
+FIXTURE = P.load(E.NAME)
 GOLD = FIXTURE["sha256"]
 SWEEP = E.sweep_entries()
 
 
-def _git(*args):
-    try:
-        r = subprocess.run(("git", "-C", ROOT) + args, capture_output=True, text=True, timeout=30)
-    except (OSError, subprocess.TimeoutExpired):
-        return None
-    return r
-
-
 def test_fixture_is_from_another_commit_and_names_every_launch():
-    """The digests were not made by the library under test: the fixture names a commit other than the one this tree's
-    library is built from -- another commit than HEAD, or, in a work tree whose HEAD is still that commit, kernel
-    sources that differ from it.  Its keys are exactly the launches of this tree."""
-    commit = FIXTURE["library_commit"]
-    assert re.fullmatch(r"[0-9a-f]{40}", commit), commit
-    head = _git("rev-parse", "HEAD")
-    if head is not None and head.returncode == 0 and head.stdout.strip() == commit:
-        diff = _git("diff", "--quiet", commit, "--", "codd_amd/csrc/conv_kernel.h", "codd_amd/csrc/conv_quad_kernel.h")
-        assert diff is not None and diff.returncode == 1, "the fixture was made by the library of this very commit"
-    keys = E.all_keys()
-    assert len(set(keys)) == len(keys)
-    assert sorted(GOLD) == sorted(keys), (sorted(set(keys) - set(GOLD))[:5], sorted(set(GOLD) - set(keys))[:5])
-    assert all(re.fullmatch(r"[0-9a-f]{64}", v) for v in GOLD.values())
+    """parent_bits.assert_from_another_commit states the rule.  The fixture's keys are exactly the launches of this tree."""
+    P.assert_from_another_commit(FIXTURE, E.SOURCES)
+    P.assert_keys(FIXTURE, P.all_keys(E))
 
 
 @pytest.mark.parametrize("L", list(SWEEP), ids=E.V.layer_id)
 def test_shipped_fp32_configurations_keep_their_bits(L):
-    bad = [key for (key, e, geom, act, operands) in SWEEP[L] if E.sweep_digest(T, e, geom, act, operands) != GOLD[key]]
+    bad = P.changed(E.sweep_digests(SWEEP[L]), GOLD, [key for (key, *_) in SWEEP[L]])
     assert not bad, ("%d of %d launches changed bits" % (len(bad), len(SWEEP[L])), bad[:4])
 
 
 def test_multi_launch_keeps_its_bits(monkeypatch):
-    got = E.multi_digests(T, monkeypatch)
-    assert got == {k: GOLD[k] for k in E.multi_keys()}, [k for k in got if got[k] != GOLD[k]]
+    got = E.multi_digests(monkeypatch)
+    assert list(got) == E.multi_keys()
+    assert not P.changed(got, GOLD, list(got))
 
 
 @pytest.mark.parametrize("name", list(E.HAND))

@@ -1,7 +1,7 @@
 """The vector epilogue of the exact-fp32 convolution kernels (conv_kernel.h conv_epilogue on swapped MFMA operands: a lane
 holds four consecutive pixels of one channel) reproduces, bit for bit, what the library of the PARENT commit produced on
 the launches of tests/conv_epilogue_vec_cases.py: tests/golden/conv_epilogue_vec_bits.json holds sha256 of the output bytes
-per launch (tools/conv_epilogue_vec_bits.py wrote it on the GPU with that library).
+per launch (tools/parent_bits.py wrote it on the GPU with that library).
 
 * bits against the parent fixture: five layers x seven output sizes x seven launch configurations, and one
   codd_conv2d_multi launch mixing a Wout % 4 == 0 job with a Wout % 4 != 0 one;
@@ -9,47 +9,24 @@ per launch (tools/conv_epilogue_vec_bits.py wrote it on the GPU with that librar
   is pinned by the fixture), the floats around every allocation untouched;
 * in place: res1 IS the output Slice -> the bits of the out-of-place launch;
 * in every launch the sentinel channels around the output Slice come back untouched and, the output being pre-filled with
-  NaN, an element that was not written shows in the digest (conv_epilogue_vec_cases.launch asserts the sentinels).
+  NaN, an element that was not written shows in the digest (conv_epilogue_cases.launch asserts the sentinels).
 A key missing from the fixture, or one the fixture has and the tree does not, fails."""
-import json
-import os
-import re
-import subprocess
-
 import pytest
 
 import conv_epilogue_vec_cases as VC
+import parent_bits as P
 import test_gpu_conv_fp64 as T
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURE = json.load(open(os.path.join(ROOT, "tests", "golden", "conv_epilogue_vec_bits.json")))
+FIXTURE = P.load(VC.NAME)
 GOLD = FIXTURE["sha256"]
 CASES = VC.cases()
 
 
-def _git(*args):
-    try:
-        r = subprocess.run(("git", "-C", ROOT) + args, capture_output=True, text=True, timeout=30)
-    except (OSError, subprocess.TimeoutExpired):
-        return None
-    return r
-
-
 def test_fixture_is_from_another_commit_and_names_every_launch():
-    """The digests were not made by the library under test (the rule of test_gpu_conv_epilogue_bits.py): the fixture names
-    a commit other than HEAD, or, in a work tree whose HEAD is still that commit, kernel sources that differ from it.  Its
-    keys are exactly the launches of this tree."""
-    commit = FIXTURE["library_commit"]
-    assert re.fullmatch(r"[0-9a-f]{40}", commit), commit
-    head = _git("rev-parse", "HEAD")
-    if head is not None and head.returncode == 0 and head.stdout.strip() == commit:
-        diff = _git("diff", "--quiet", commit, "--", "codd_amd/csrc/conv_kernel.h", "codd_amd/csrc/conv_quad_kernel.h")
-        assert diff is not None and diff.returncode == 1, "the fixture was made by the library of this very commit"
-    keys = VC.all_keys()
-    assert len(set(keys)) == len(keys)
-    assert sorted(GOLD) == sorted(keys), (sorted(set(keys) - set(GOLD))[:5], sorted(set(GOLD) - set(keys))[:5])
-    assert all(re.fullmatch(r"[0-9a-f]{64}", v) for v in GOLD.values())
+    """parent_bits.assert_from_another_commit states the rule.  The fixture's keys are exactly the launches of this tree."""
+    P.assert_from_another_commit(FIXTURE, VC.SOURCES)
+    P.assert_keys(FIXTURE, P.all_keys(VC))
 
 
 def test_cases_reach_every_decision():
@@ -70,13 +47,14 @@ def test_cases_reach_every_decision():
 def test_cases_keep_the_parents_bits(name, hw):
     mine = [c for c in CASES if c[1] == name and (c[2], c[3]) == hw]
     assert len(mine) >= 3
-    bad = [key for (key, *rest) in mine if VC.digest(VC.launch(*rest)) != GOLD[key]]
+    bad = P.changed({key: VC.digest(VC.launch(*rest)) for (key, *rest) in mine}, GOLD, [c[0] for c in mine])
     assert not bad, ("%d of %d launches changed bits" % (len(bad), len(mine)), bad)
 
 
 def test_multi_launch_with_a_flag_per_job_keeps_its_bits():
     got = VC.multi_digests()
-    assert got == {k: GOLD[k] for k in VC.multi_keys()}, [k for k in got if got[k] != GOLD[k]]
+    assert list(got) == VC.multi_keys()
+    assert not P.changed(got, GOLD, list(got))
 
 
 @pytest.mark.parametrize("layout", [0, 1])

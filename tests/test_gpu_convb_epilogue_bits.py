@@ -1,6 +1,6 @@
 """The epilogues of the split-bf16 convolution kernel (conv_bf16_kernel.h) reproduce, bit for bit, what the library of the
 PARENT commit wrote on the launches of tests/convb_epilogue_cases.py: tests/golden/convb_epilogue_bits.json holds sha256 of
-the written bytes per launch (tools/convb_epilogue_bits.py made it on the GPU with that library).
+the written bytes per launch (tools/parent_bits.py made it on the GPU with that library).
 
 * every wave grid X(PGW, CGW, A, B, KS) of CONVB_ALL x terms 1 | 3 | 16 | 48 x three maps: record output without a gate
   (cout 64 | 18, bias | none, relu | none, three borders, a channel offset), the three gate epilogues (gate 2 with G = 16
@@ -10,52 +10,32 @@ the written bytes per launch (tools/convb_epilogue_bits.py made it on the GPU wi
 * a bias 4 bytes off a 16-byte boundary is refused with CODD_EINVAL;
 * the case list reaches every branch (no GPU needed), and the fixture is not from the library under test.
 A key missing from the fixture, or one the fixture has and the tree does not, fails."""
-import json
 import os
 import re
-import subprocess
 
 import pytest
 
 import convb_epilogue_cases as BC
+import parent_bits as P
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURE = json.load(open(os.path.join(ROOT, "tests", "golden", "convb_epilogue_bits.json")))
+FIXTURE = P.load(BC.NAME)
 GOLD = FIXTURE["sha256"]
 CASES = BC.cases()
 gpu = pytest.mark.gpu
 
 
-def _git(*args):
-    try:
-        r = subprocess.run(("git", "-C", ROOT) + args, capture_output=True, text=True, timeout=30)
-    except (OSError, subprocess.TimeoutExpired):
-        return None
-    return r
-
-
 @gpu
 def test_fixture_is_from_another_commit_and_names_every_launch():
-    """The digests were not made by the library under test (the rule of test_gpu_conv_epilogue_vec_bits.py): the fixture
-    names a commit other than HEAD, or, in a work tree whose HEAD is still that commit, a kernel source that differs from
-    it.  Its keys are exactly the launches of this tree."""
-    commit = FIXTURE["library_commit"]
-    assert re.fullmatch(r"[0-9a-f]{40}", commit), commit
-    head = _git("rev-parse", "HEAD")
-    if head is not None and head.returncode == 0 and head.stdout.strip() == commit:
-        diff = _git("diff", "--quiet", commit, "--", "codd_amd/csrc/conv_bf16_kernel.h")
-        assert diff is not None and diff.returncode == 1, "the fixture was made by the library of this very commit"
-    keys = BC.all_keys()
-    assert len(set(keys)) == len(keys)
-    assert sorted(GOLD) == sorted(keys), (sorted(set(keys) - set(GOLD))[:5], sorted(set(GOLD) - set(keys))[:5])
-    assert all(re.fullmatch(r"[0-9a-f]{64}", v) for v in GOLD.values())
+    """parent_bits.assert_from_another_commit states the rule.  The fixture's keys are exactly the launches of this tree."""
+    P.assert_from_another_commit(FIXTURE, BC.SOURCES)
+    P.assert_keys(FIXTURE, P.all_keys(BC))
 
 
 def test_cases_reach_every_branch():
     """No GPU needed.  The case list names exactly the instantiations of CONVB_ALL in the header, each in the four operand
     formats on the three maps; the maps hold partial tiles in both axes, a unit valid for a few lanes only and empty
     units; the record cases take the 16-byte and the per-element bias path, the gates all three tile kinds of gate 2."""
-    src = open(os.path.join(ROOT, "codd_amd", "csrc", "conv_bf16_kernel.h")).read()
+    src = open(os.path.join(P.ROOT, "codd_amd", "csrc", "conv_bf16_kernel.h")).read()
     groups = dict(re.findall(r"#define CONVB_GROUP_(\w)\(X\) (.*)", src))
     listed = re.search(r"#define CONVB_ALL\(X\)(.*?)\n#define", src, re.S).group(1)
     header = [tuple(int(v) for v in x) for gname in re.findall(r"CONVB_GROUP_(\w)\(X\)", listed)
@@ -85,7 +65,7 @@ def test_cases_reach_every_branch():
 def test_cases_keep_the_parents_bits(X, terms):
     mine = [c for c in CASES if c[1] == X and c[4] == terms]
     assert len(mine) == 3 * len(BC.case_names(X))
-    bad = [key for (key, *rest) in mine if BC.launch(*rest) != GOLD[key]]
+    bad = P.changed(BC.case_digests(mine), GOLD, [c[0] for c in mine])
     assert not bad, ("%d of %d launches changed bits" % (len(bad), len(mine)), bad)
 
 
@@ -108,7 +88,7 @@ def test_gate3_in_place_gives_the_bits_of_out_of_place(X):
                 zq, h = BC._c4(d["zq", 2 * G]), BC._c4(d["h", G])
                 out = h if in_place else BC._c4(torch.full((BC.B, G, H, W), float("nan")))
                 key = ("gate", 3, H, W, BC.B, 1, 1, 0, terms)
-                BC._forced(pc, key, cfg, lambda: ops.conv_gate(pc, xs, 3, pad=1, out=out, res1=zq, post=h, xs_out=rec))
+                P.forced(pc, key, cfg, lambda: ops.conv_gate(pc, xs, 3, pad=1, out=out, res1=zq, post=h, xs_out=rec))
                 res.append(BC.digest(out.buf, rec.buf))
             assert res[0] == res[1], (X, terms)
         finally:

@@ -1,22 +1,18 @@
 """No GPU needed: tests/golden/ingest_bits.json names exactly the launches of tests/ingest_cases.py, and those launches
 reach what the ingest kernel branches on."""
-import json
-import os
 import re
 
 import numpy as np
 
 import ingest_cases as IC
 import live_fmt_ref as fr
+import parent_bits as P
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURE = json.load(open(os.path.join(ROOT, "tests", "golden", "ingest_bits.json")))
+FIXTURE = P.load(IC.NAME)
 
 
 def test_fixture_keys_are_the_case_list():
-    keys = IC.all_keys()
-    assert len(set(keys)) == len(keys)
-    assert list(FIXTURE["sha256"]) == keys, (sorted(set(keys) - set(FIXTURE["sha256"]))[:5], sorted(set(FIXTURE["sha256"]) - set(keys))[:5])
+    P.assert_keys(FIXTURE, P.all_keys(IC))
     assert re.fullmatch(r"[0-9a-f]{40}", FIXTURE["library_commit"])
     assert all(re.fullmatch(r"[0-9a-f]{64}", v) for v in FIXTURE["sha256"].values())
 
@@ -30,7 +26,7 @@ def test_shapes_take_both_store_paths_and_every_entry_and_format():
     assert {y for f, y in IC.FRAME_FORMATS if f == "nv12"} == set(fr.YUV)
     assert {f for f, _ in IC.CALIB_FORMATS} == {"rgb8"} | set(fr.FORMATS) and ("rgb8", True) in IC.CALIB_FORMATS
     assert [s[1] % 4 for s in IC.MAP_SHAPES] == [2, 1] and set(IC.MODELS) == {"brown", "fisheye"}
-    kinds = {k.split("/")[3] for k in IC.all_keys() if k.startswith("frames/")}
+    kinds = {k.split("/")[3] for k in P.all_keys(IC) if k.startswith("frames/")}
     assert kinds == set(IC.FRAME_KINDS) >= set(IC.PAIR_KINDS)
 
 

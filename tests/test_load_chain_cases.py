@@ -1,24 +1,21 @@
 """No GPU needed: tests/golden/load_chain_bits.json names exactly the launches of tests/load_chain_cases.py, and those
 launches reach what the batched loads of motion.hip branch on."""
-import json
 import os
 import re
 
 import load_chain_cases as LC
+import parent_bits as P
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURE = json.load(open(os.path.join(ROOT, "tests", "golden", "load_chain_bits.json")))
+FIXTURE = P.load(LC.NAME)
 
 
 def _source_define(name):
-    src = open(os.path.join(ROOT, "codd_amd", "csrc", "motion.hip")).read()
+    src = open(os.path.join(P.ROOT, "codd_amd", "csrc", "motion.hip")).read()
     return int(re.search(r"^#define %s (\d+)" % name, src, re.M).group(1))
 
 
 def test_fixture_keys_are_the_case_list():
-    keys = LC.all_keys()
-    assert len(set(keys)) == len(keys)
-    assert list(FIXTURE["sha256"]) == keys, (sorted(set(keys) - set(FIXTURE["sha256"]))[:5], sorted(set(FIXTURE["sha256"]) - set(keys))[:5])
+    P.assert_keys(FIXTURE, P.all_keys(LC))
     assert re.fullmatch(r"[0-9a-f]{40}", FIXTURE["library_commit"])
     assert all(re.fullmatch(r"[0-9a-f]{64}", v) for v in FIXTURE["sha256"].values())
 
