@@ -64,6 +64,8 @@ SIGNATURES = {
     "codd_abi_version": (_i, []),
     "codd_conv2d": (_i, [C.POINTER(ConvParams), _p]),
     "codd_conv2d_check": (_i, [C.POINTER(ConvParams)]),
+    "codd_conv2d_lds_bytes": (_ll, [C.POINTER(ConvParams)]),
+    "codd_conv2d_bf16_instantiations": (_i, [C.POINTER(_i), _i]),
     "codd_conv2d_multi": (_i, [C.POINTER(ConvParams), _i, _p]),
     "codd_roll_packed_size": (_ll, [_i, _i, _i]),
     "codd_roll_pack_weights": (_i, [_p, _p, _i, _i, _i, _i, _p]),
@@ -138,7 +140,7 @@ SIGNATURES = {
     "codd_export_confidence": (_i, [_p, _p, _p, _i, _i, _i, _i, c_float_p, _f, _f, _p, _p, _p]),
 }
 
-ABI_VERSION = 12  # CODD_ABI_VERSION of include/codd_hip.h
+ABI_VERSION = 13  # CODD_ABI_VERSION of include/codd_hip.h
 _lib = None
 LOADED = None  # path of the library this process loaded
 MISSING = []

@@ -97,7 +97,8 @@ extern "C" int codd_conv2d_pack_weights(const float* w, float* wpacked, int Cout
 }
 
 template <int NW, int NPB, int MB, int WREG, int IREG>
-static int launch_conv(const ConvK& k, size_t lds, int grid, hipStream_t s) {
+static int launch_conv(const ConvK& k, size_t lds, int grid, hipStream_t s, int dry) {
+  if (dry) return CODD_OK;
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)conv_mfma_kernel<NW, NPB, MB, WREG, IREG>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -109,13 +110,13 @@ static int launch_conv(const ConvK& k, size_t lds, int grid, hipStream_t s) {
 }
 
 template <int NPB, int MB>
-static int launch_conv_regs(const ConvK& k, size_t lds, int grid, hipStream_t s) {
+static int launch_conv_regs(const ConvK& k, size_t lds, int grid, hipStream_t s, int dry) {
   const int wr = cdiv(k.wchunk >> 2, 256), ir = cdiv(k.nunits, 256);
-  if (wr <= 4 && ir <= 4) return launch_conv<4, NPB, MB, 4, 4>(k, lds, grid, s);
-  if (wr <= 4 && ir <= 8) return launch_conv<4, NPB, MB, 4, 8>(k, lds, grid, s);
-  if (wr <= 12 && ir <= 4) return launch_conv<4, NPB, MB, 12, 4>(k, lds, grid, s);
-  if (wr <= 12 && ir <= 8) return launch_conv<4, NPB, MB, 12, 8>(k, lds, grid, s);
-  if (wr <= 16 && ir <= 8) return launch_conv<4, NPB, MB, 16, 8>(k, lds, grid, s);
+  if (wr <= 4 && ir <= 4) return launch_conv<4, NPB, MB, 4, 4>(k, lds, grid, s, dry);
+  if (wr <= 4 && ir <= 8) return launch_conv<4, NPB, MB, 4, 8>(k, lds, grid, s, dry);
+  if (wr <= 12 && ir <= 4) return launch_conv<4, NPB, MB, 12, 4>(k, lds, grid, s, dry);
+  if (wr <= 12 && ir <= 8) return launch_conv<4, NPB, MB, 12, 8>(k, lds, grid, s, dry);
+  if (wr <= 16 && ir <= 8) return launch_conv<4, NPB, MB, 16, 8>(k, lds, grid, s, dry);
   return CODD_EUNSUPPORTED;
 }
 
@@ -124,15 +125,16 @@ static int launch_conv_regs(const ConvK& k, size_t lds, int grid, hipStream_t s)
 // waves, exactly 256 with 9: the weights of a chunk are then fetched once per 9 rows instead of per 4).  2 and
 // 8: more / fewer, smaller / larger workgroups for the autotuner (tiny maps, 144- and 288-row maps).
 template <int NW, int MB>
-static int launch_conv_nwx(const ConvK& k, size_t lds, int grid, hipStream_t s) {
+static int launch_conv_nwx(const ConvK& k, size_t lds, int grid, hipStream_t s, int dry) {
   const int wr = cdiv(k.wchunk >> 2, NW * 64), ir = cdiv(k.nunits, NW * 64);
-  if (wr <= 8 && ir <= 4) return launch_conv<NW, 1, MB, 8, 4>(k, lds, grid, s);
-  if (wr <= 16 && ir <= 4) return launch_conv<NW, 1, MB, 16, 4>(k, lds, grid, s);
+  if (wr <= 8 && ir <= 4) return launch_conv<NW, 1, MB, 8, 4>(k, lds, grid, s, dry);
+  if (wr <= 16 && ir <= 4) return launch_conv<NW, 1, MB, 16, 4>(k, lds, grid, s, dry);
   return CODD_EUNSUPPORTED;
 }
 
 template <int NW, int NPB, int MB, int WREG, int QREG>
-static int launch_quad(const ConvK& k, size_t lds, int grid, hipStream_t s) {
+static int launch_quad(const ConvK& k, size_t lds, int grid, hipStream_t s, int dry) {
+  if (dry) return CODD_OK;
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)conv_quad_kernel<NW, NPB, MB, WREG, QREG>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -144,10 +146,10 @@ static int launch_quad(const ConvK& k, size_t lds, int grid, hipStream_t s) {
 }
 
 // quad-layout dispatch: wr / qr = float4 of weights / quad units of input per thread and chunk
-static int launch_quad_any(const ConvK& k, int nw, size_t lds, int grid, hipStream_t s) {
+static int launch_quad_any(const ConvK& k, int nw, size_t lds, int grid, hipStream_t s, int dry) {
   const codd_conv_params& p = k.p;
   const int nt = nw * 64, wr = cdiv(k.wchunk >> 2, nt), qr = cdiv((p.ck >> 2) * k.upc, nt);
-#define Q(W, N, M, R, QQ) if (nw == W && p.npb == N && p.mb == M && wr <= R && qr <= QQ) return launch_quad<W, N, M, R, QQ>(k, lds, grid, s);
+#define Q(W, N, M, R, QQ) if (nw == W && p.npb == N && p.mb == M && wr <= R && qr <= QQ) return launch_quad<W, N, M, R, QQ>(k, lds, grid, s, dry);
   Q(4, 1, 1, 8, 2) Q(4, 1, 2, 8, 1) Q(4, 1, 2, 16, 2) Q(4, 1, 4, 12, 1) Q(4, 1, 4, 16, 2)
   Q(4, 2, 1, 8, 2) Q(4, 2, 2, 8, 2) Q(4, 2, 2, 16, 2) Q(4, 2, 4, 12, 2) Q(4, 2, 4, 16, 2)
   Q(4, 4, 1, 8, 4) Q(4, 4, 2, 8, 4)
@@ -156,20 +158,22 @@ static int launch_quad_any(const ConvK& k, int nw, size_t lds, int grid, hipStre
   return CODD_EUNSUPPORTED;
 }
 
-/* staging limits the host heuristics must respect: <= 16 float4 of weights and <= 8 float4 of input
- * per thread and chunk (codd_conv2d returns CODD_EUNSUPPORTED otherwise) */
-int codd_conv2d_bf16(const codd_conv_params* pp, void* stream, int dry_run);  // conv_bf16.hip
+/* (the staging limits above -- float4 of weights and of input per thread and chunk -- are not restated by the host
+ * heuristics: they ask codd_conv2d_lds_bytes) */
+/* layout 2: the return code of the launch; dry_run: the dynamic LDS bytes instead of the launch, or the negative code */
+long long codd_conv2d_bf16(const codd_conv_params* pp, void* stream, int dry_run);  // conv_bf16.hip
 
-extern "C" int codd_conv2d_check(const codd_conv_params* pp) {
-  if (!pp || pp->layout != 2) return CODD_EINVAL;
-  return codd_conv2d_bf16(pp, nullptr, 1);
-}
-
-/* launch geometry of the exact-fp32 kernels (layouts 0 and 1) for ``pp`` */
-static int conv_fill(const codd_conv_params* pp, ConvK& k, size_t& lds, long long& grid, int& nw) {
+/* launch geometry of the exact-fp32 kernels (layouts 0 and 1) for ``pp``.  dry: no pointer field of ``pp`` is read -- the
+ * copy in ``k`` has them null, which the alignment predicates below take as aligned */
+static int conv_fill(const codd_conv_params* pp, ConvK& k, size_t& lds, long long& grid, int& nw, int dry) {
   k.p = *pp;
+  if (dry) {
+    k.p.in0.ptr = k.p.in1.ptr = k.p.res1.ptr = k.p.res2.ptr = k.p.post.ptr = k.p.wpacked = k.p.bias = nullptr;
+    k.p.out = nullptr;
+  }
   const codd_conv_params& p = k.p;
-  if (!p.in0.ptr || !p.out || !p.wpacked || p.C0 <= 0 || p.C1 < 0 || (p.C1 > 0 && !p.in1.ptr)) return CODD_EINVAL;
+  if (!dry && (!p.in0.ptr || !p.out || !p.wpacked || (p.C1 > 0 && !p.in1.ptr))) return CODD_EINVAL;
+  if (p.C0 <= 0 || p.C1 < 0) return CODD_EINVAL;
   if (p.ck < 4 || (p.ck & 3) || p.B < 1 || p.Cout < 1 || p.kh < 1 || p.kw < 1 || p.pad_l < 0 || p.pad_t < 0)
     return CODD_EINVAL;
   if (!(p.mb == 1 || p.mb == 2 || p.mb == 4) || !(p.npb == 1 || p.npb == 2 || p.npb == 4)) return CODD_EINVAL;
@@ -221,35 +225,49 @@ static int conv_fill(const codd_conv_params* pp, ConvK& k, size_t& lds, long lon
   return CODD_OK;
 }
 
-extern "C" int codd_conv2d(const codd_conv_params* pp, void* stream) {
-  if (!pp) return CODD_EINVAL;
-  if (pp->layout != 2 && (pp->dil2 || pp->gate)) return CODD_EUNSUPPORTED;  // dual tap sets / gate epilogues: layout 2 only
-  if (pp->layout == 2) {
-    const codd_conv_params& q = *pp;
-    if (!q.xs || (!q.out && !q.xso) || !q.wpacked || q.C0 <= 0 || q.C1 < 0 || q.B < 1 || q.Cout < 1 || q.kh < 1 || q.kw < 1 ||
-        q.pad_l < 0 || q.pad_t < 0)
-      return CODD_EINVAL;
-    if (q.store_mode && (q.kh != 1 || q.kw != 1 || q.res1.ptr || q.res2.ptr || q.post.ptr)) return CODD_EUNSUPPORTED;
-    return codd_conv2d_bf16(pp, stream, 0);
-  }
-  ConvK k;
-  size_t lds;
-  long long grid;
-  int nw;
-  const int rc = conv_fill(pp, k, lds, grid, nw);
-  if (rc != CODD_OK) return rc;
+/* the register class of an exact-fp32 launch (layouts 0 and 1), launched unless dry */
+static int conv_dispatch(const ConvK& k, int nw, size_t lds, int grid, hipStream_t s, int dry) {
   const codd_conv_params& p = k.p;
-  hipStream_t s = (hipStream_t)stream;
-  if (p.layout == 1) return launch_quad_any(k, nw, lds, (int)grid, s);
-#define CASEW(W, M) if (nw == W && p.mb == M) return launch_conv_nwx<W, M>(k, lds, (int)grid, s)
+  if (p.layout == 1) return launch_quad_any(k, nw, lds, grid, s, dry);
+#define CASEW(W, M) if (nw == W && p.mb == M) return launch_conv_nwx<W, M>(k, lds, grid, s, dry)
   CASEW(9, 1); CASEW(9, 2); CASEW(9, 4); CASEW(2, 1); CASEW(2, 2); CASEW(2, 4); CASEW(8, 1); CASEW(8, 2); CASEW(8, 4);
 #undef CASEW
-#define CASE(N, M) if (p.npb == N && p.mb == M) return launch_conv_regs<N, M>(k, lds, (int)grid, s)
+#define CASE(N, M) if (p.npb == N && p.mb == M) return launch_conv_regs<N, M>(k, lds, grid, s, dry)
   CASE(1, 1); CASE(1, 2); CASE(1, 4);
   CASE(2, 1); CASE(2, 2); CASE(2, 4);
   CASE(4, 1); CASE(4, 2); CASE(4, 4);
 #undef CASE
   return CODD_EUNSUPPORTED;
+}
+
+/* codd_conv2d (dry = 0: its return code) and codd_conv2d_lds_bytes (dry = 1: every check of the launch that reads no
+ * pointer, then the dynamic LDS bytes instead of the launch) */
+static long long conv_any(const codd_conv_params* pp, void* stream, int dry) {
+  if (!pp) return CODD_EINVAL;
+  if (pp->layout != 2 && (pp->dil2 || pp->gate)) return CODD_EUNSUPPORTED;  // dual tap sets / gate epilogues: layout 2 only
+  if (pp->layout == 2) {
+    const codd_conv_params& q = *pp;
+    if (!dry && (!q.xs || (!q.out && !q.xso) || !q.wpacked)) return CODD_EINVAL;
+    if (q.C0 <= 0 || q.C1 < 0 || q.B < 1 || q.Cout < 1 || q.kh < 1 || q.kw < 1 || q.pad_l < 0 || q.pad_t < 0) return CODD_EINVAL;
+    if (q.store_mode && (q.kh != 1 || q.kw != 1 || (!dry && (q.res1.ptr || q.res2.ptr || q.post.ptr)))) return CODD_EUNSUPPORTED;
+    return codd_conv2d_bf16(pp, stream, dry);
+  }
+  ConvK k;
+  size_t lds;
+  long long grid;
+  int nw;
+  int rc = conv_fill(pp, k, lds, grid, nw, dry);
+  if (rc == CODD_OK) rc = conv_dispatch(k, nw, lds, (int)grid, (hipStream_t)stream, dry);
+  return dry && rc == CODD_OK ? (long long)lds : rc;
+}
+
+extern "C" int codd_conv2d(const codd_conv_params* pp, void* stream) { return (int)conv_any(pp, stream, 0); }
+
+extern "C" long long codd_conv2d_lds_bytes(const codd_conv_params* pp) { return conv_any(pp, nullptr, 1); }
+
+extern "C" int codd_conv2d_check(const codd_conv_params* pp) {
+  const long long lds = codd_conv2d_lds_bytes(pp);
+  return lds >= 0 ? CODD_OK : (int)lds;
 }
 
 template <int NW, int NPB, int MB, int WREG, int QREG>
@@ -280,7 +298,7 @@ extern "C" int codd_conv2d_multi(const codd_conv_params* ps, int n, void* stream
     long long g;
     int nw;
     if (ps[i].layout != 1) return CODD_EUNSUPPORTED;
-    const int rc = conv_fill(&ps[i], kn.k[i], l, g, nw);
+    const int rc = conv_fill(&ps[i], kn.k[i], l, g, nw, 0);
     if (rc != CODD_OK) return rc;
     const codd_conv_params& p = kn.k[i].p;
     if (nw != 4 || p.npb != 1 || p.mb != ps[0].mb || !(p.mb == 1 || p.mb == 2)) return CODD_EUNSUPPORTED;

@@ -66,8 +66,21 @@ static int launch_b(const ConvB& k, size_t lds, int grid, hipStream_t s) {
   return CODD_OK;
 }
 
-/* layout 2 of codd_conv2d */
-int codd_conv2d_bf16(const codd_conv_params* pp, void* stream, int dry_run) {
+/* the instantiations (pgw, cgw, A, B, ksplit), in the order of the dispatch below */
+extern "C" int codd_conv2d_bf16_instantiations(int* out, int cap) {
+  static const int all[][5] = {
+#define X(PGW, CGW, A, B, KS) {PGW, CGW, A, B, KS},
+      CONVB_ALL(X)
+#undef X
+  };
+  const int n = (int)(sizeof(all) / sizeof(all[0]));
+  for (int i = 0; out && i < n && i < cap; ++i)
+    for (int j = 0; j < 5; ++j) out[5 * i + j] = all[i][j];
+  return n;
+}
+
+/* layout 2 of codd_conv2d: its return code; dry_run: the dynamic LDS bytes instead of the launch, or the negative code */
+long long codd_conv2d_bf16(const codd_conv_params* pp, void* stream, int dry_run) {
   ConvB k;
   size_t lds;
   long long grid;
@@ -79,7 +92,7 @@ int codd_conv2d_bf16(const codd_conv_params* pp, void* stream, int dry_run) {
   const int ks = p.ksplit == 2 ? 2 : 1;
 #define X(PGW, CGW, A, B, KS)                                                                    \
   if (p.pgw == PGW && p.cgw == CGW && a == A && bb == B && ks == KS)                             \
-    return dry_run ? CODD_OK                                                                     \
+    return dry_run ? (long long)lds                                                              \
            : (p.xso || p.gate) ? (p.terms == 3   ? launch_b<PGW, CGW, A, B, 3, 1, KS>(k, lds, (int)grid, s)   \
                                   : p.terms == 48 ? launch_b<PGW, CGW, A, B, 48, 1, KS>(k, lds, (int)grid, s)  \
                                   : p.terms == 16 ? launch_b<PGW, CGW, A, B, 16, 1, KS>(k, lds, (int)grid, s)  \

@@ -5,6 +5,7 @@ libcodd_hip.so.  There is no CPU / eager fallback: tensors must live on a ROCm d
 """
 import collections
 import ctypes as C
+import functools
 
 import torch
 
@@ -177,10 +178,6 @@ import os as _os
 _FORCE_NW = 0  # (tests: a workgroup height the heuristic may not pick)
 
 
-def _wrow(mb):
-    return 16 * mb + (0 if mb & 1 else 16)
-
-
 def _pick_nw(pc, npb, Hout, Wout, B, ncog):
     """Waves (= 16-pixel tile rows) per workgroup: 4, or 9 where that removes a nearly empty last round.
     The 256 CUs take workgroups round-robin, so a launch lasts about ceil(grid / 256) rounds of nw rows;
@@ -201,30 +198,26 @@ def _conv_cfg(pc, Hout, Wout, B, sy, sx, dy, dx, pl):
 
     Measured on MI355X (tools/time_ops.py): the small 4x16-pixel tile (npb = 1) wins on every
     layer with more than 16 output channels -- the kernel is latency / barrier bound, so more
-    resident workgroups beat operand re-use; 16-channel layers prefer 4x32.  The LDS chunk is sized
-    so that the whole grid is resident at once when possible (a 576-block grid at 2 blocks/CU runs
-    a second, nearly empty round: 112 us vs 67 us for 504 blocks).  Limits of the kernel's register
-    staging: <= 16 float4 of weights and <= 8 float4 of input per thread and chunk."""
+    resident workgroups beat operand re-use; 16-channel layers prefer 4x32.  The LDS chunk is the deepest
+    the library accepts (codd_conv2d_lds_bytes: the register staging of the instantiated kernels) whose LDS
+    lets the whole grid be resident at once when possible (a 576-block grid at 2 blocks/CU runs
+    a second, nearly empty round: 112 us vs 67 us for 504 blocks)."""
+    lib = _abi.load()
     ncog = -(-pc.cout_eff // (16 * pc.mb))
     npb = 2 if pc.cout_eff <= 16 else 1
     nw = _pick_nw(pc, npb, Hout, Wout, B, ncog)
-    nt = 64 * nw
     xb = 2 if npb >= 2 else 1
     th, tw = nw * (npb // xb), 16 * xb
     grid = (-(-Hout // th)) * (-(-Wout // tw)) * ncog * B
     per_cu = min(max(-(-grid // 256), 2 if nw == 4 else 1), 4)
     budget = min(64 * 1024, (160 * 1024) // per_cu - 512)
-    thi = (th - 1) * sy + (pc.kh - 1) * dy + 1
-    twi = (tw - 1) * sx + (pc.kw - 1) * dx + 1
-    xoff = (4 - pl % 4) % 4
-    twp = -(-(xoff + twi) // 4) * 4
-    per = thi * twp
-    chs = ((per + 15) // 32) * 32 + 16 if sx == 1 else per + 4
-    cin_pad = -(-pc.cin // 4) * 4
-    ck = min(cin_pad, 32)
-    taps = pc.kh * pc.kw
-    while ck > 4 and ((taps * ck * _wrow(pc.mb) + ck * chs) * 4 > budget or taps * ck * _wrow(pc.mb) > 64 * nt
-                      or ck * thi * (twp // 4) > (8 if nw == 4 else 4) * nt):
+    # (a dry run: the input size is no part of the launch geometry of layout 0)
+    p = _conv_params(pc, B, pc.cin, 0, 0, 0, Hout, Wout, (sy, sx), (pl, pl), (dy, dx))
+    ck = min(-(-pc.cin // 4) * 4, 32)
+    while ck > 4:
+        _set_cfg(p, (npb, nw, ck, pc.mb, 0))
+        if 0 <= lib.codd_conv2d_lds_bytes(C.byref(p)) <= budget:
+            break
         ck -= 4
     return npb, nw, ck
 
@@ -334,13 +327,24 @@ def _small_footprint(cands):
     return small or cands
 
 
-# split-bf16 kernel instantiations (conv_bf16_kernel.h): (pgw, cgw, A, B) and the tiles (rows, units per row) tried
-_B_INST = ((2, 2, 5, 2, 1), (4, 1, 4, 4, 1), (4, 1, 4, 2, 1), (4, 1, 4, 1, 1), (4, 1, 8, 1, 1), (4, 1, 2, 2, 1),
-           (4, 1, 2, 1, 1), (4, 1, 3, 4, 1), (4, 1, 3, 2, 1),
-           # 8 consumer waves (two per SIMD): k-split pairs (ks = 2) and 4x2 wave grids that split the tile
-           (2, 2, 5, 2, 2), (4, 1, 4, 2, 2), (4, 1, 3, 2, 2), (4, 1, 3, 4, 2), (4, 2, 4, 2, 1), (4, 2, 3, 2, 1),
-           (8, 1, 4, 4, 1))
-# tiles (rows, 16-pixel units per row) by pixel units of a workgroup (= pgw * a)
+@functools.lru_cache(maxsize=None)
+def _b_inst():
+    """The split-bf16 kernel instantiations (pgw, cgw, A, B, ksplit) of the library, in the order of CONVB_ALL
+    (conv_bf16_kernel.h).  ``ops._B_INST`` reads the same tuple; importing this module loads no library."""
+    lib = _abi.load()
+    n = lib.codd_conv2d_bf16_instantiations(None, 0)
+    flat = (C.c_int * (5 * n))()
+    lib.codd_conv2d_bf16_instantiations(flat, n)
+    return tuple(tuple(flat[5 * i:5 * i + 5]) for i in range(n))
+
+
+def __getattr__(name):
+    if name == "_B_INST":
+        return _b_inst()
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+# the tiles (rows, 16-pixel units per row) tried, by pixel units of a workgroup (= pgw * A of an instantiation)
 _B_TILES = {10: ((9, 1), (10, 1), (5, 2)), 16: ((8, 2), (16, 1)), 32: ((16, 2),), 8: ((4, 2), (8, 1)), 12: ((12, 1), (6, 2))}
 # (round 6 added 96-channel groups (4,2,3,3) / (2,2,5,3) and 20-unit tiles (4,2,5,2) so that the 384-channel gate-input convolution
 # -- 288 workgroups = 1.12 dispatch rounds on its 64-channel x 12-unit grid -- could run as ONE round: every single-round
@@ -354,7 +358,7 @@ def _bf16_candidates(pc, Hout, Wout, B, taps, terms):
     fewest dispatch rounds over the 256 CUs times work per workgroup, larger channel groups and deeper chunks first."""
     nblk = -(-pc.cout_eff // 16)
     cands = []
-    for (pgw, cgw, a, b, ks) in _B_INST:
+    for (pgw, cgw, a, b, ks) in _b_inst():
         mb = b * cgw
         if mb > 1 and mb // 2 >= nblk:  # a channel group at least twice as wide as the layer
             continue
@@ -387,9 +391,9 @@ class SplitTensor:
 
 
 def _split_rows(H):
-    """Image rows of a shared split tensor: enough for the row overhang of EVERY instantiated tile height
-    (4, 5, 6, 8, 9, 10, 12, 16 rows: ceil(H / th) * th <= H + th - 1)."""
-    return max(-(-H // th) * th for th in (4, 5, 6, 8, 9, 10, 12, 16))
+    """Image rows of a shared split tensor: enough for the row overhang of EVERY tile height of _B_TILES
+    (4 ... 16 rows: ceil(H / th) * th <= H + th - 1)."""
+    return max(-(-H // th) * th for tiles in _B_TILES.values() for (th, _) in tiles)
 
 
 def split_input(x, x2=None, border=0, c8=None, hp=None, wp=None, out=None):
@@ -466,6 +470,162 @@ def _attach_xso(p, st, coff):
     p.xso_bt, p.xso_bl, p.xso_o8, p.xso_terms = st.bt, st.bl, coff // 8, st.terms
 
 
+def _conv_geometry(pc, Hin, Win, stride=1, pad=0, dil=1, pad_tl=None, out_hw=None):
+    """-> (sy, sx), (pad top, pad left), (dy, dx), (Hout, Wout, up) of a convolution by ``pc`` of a Hin x Win map.
+    stride / pad / dil: an int or a (y, x) pair; ``pad_tl`` = (top, left, bottom, right) for unequal borders; ``out_hw``
+    overrides the output map.  A transposed convolution (k2 s2 as a 1x1 with 4 Cout outputs) keeps the input map and
+    stores it up = 2 times as large."""
+    sy, sx = (stride, stride) if isinstance(stride, int) else stride
+    dy, dx = (dil, dil) if isinstance(dil, int) else dil
+    if pad_tl is None:
+        pt, pl = (pad, pad) if isinstance(pad, int) else pad
+        pb, pr = pt, pl
+    else:
+        pt, pl, pb, pr = pad_tl
+    if pc.deconv:
+        Hout, Wout = Hin, Win
+    elif out_hw is not None:
+        Hout, Wout = out_hw
+    else:
+        Hout = (Hin + pt + pb - dy * (pc.kh - 1) - 1) // sy + 1
+        Wout = (Win + pl + pr - dx * (pc.kw - 1) - 1) // sx + 1
+    return (sy, sx), (pt, pl), (dy, dx), (Hout, Wout, 2 if pc.deconv else 1)
+
+
+# A launch shape is looked up under two names: its ``key`` in pc.tuned (this layer object) and its signature string in
+# TUNE_DB and the shipped codd_amd/tuned/mi355x.json (any layer of that description).  The strings are the keys of the
+# shipped db, so they never change by a byte; tests/conv_fp64.py (parse_sig) and tests/test_conv_launch_config.py (_layer)
+# read them back.
+#   plain  key  (Hout, Wout, B, sy, sx, dy, dx, pl, two inputs, terms[, "split"][, "co"])
+#          sig  [b<terms>|]cout_eff,cin,kh,kw,mb,deconv|Hout,Wout,B,sy,sx,dy,dx,pl,two inputs[|split][|co]
+#               "b<terms>|" is absent under the exact-fp32 precision (terms 0); "split": pinned to the split-bf16 kernel
+#               (input or output in record form); "co": chosen under ops.coresident()
+#   gate   key  ("gate", gate, H, W, B, pad, dil, dil2, terms)
+#          sig  g<gate>,b<terms>|cout,cin,kh,kw|H,W,B,pad,dil,dil2
+def _plain_key(geom, two, terms, pinned):
+    return geom + (two, terms) + (("split",) if pinned else ()) + (("co",) if _CORESIDENT and terms else ())
+
+
+def _plain_sig(pc, key):
+    return ("b%d|" % key[9] if key[9] else "") + "%d,%d,%d,%d,%d,%d|" % (
+        pc.cout_eff, pc.cin, pc.kh, pc.kw, pc.mb, int(pc.deconv)) + ",".join(str(int(v)) for v in key[:9]) + "".join(
+            "|" + flag for flag in key[10:])
+
+
+def _gate_key(gate, H, W, B, pad, dil, dil2, terms):
+    return ("gate", gate, H, W, B, pad, dil, dil2, terms)
+
+
+def _gate_sig(pc, key):
+    _, gate, H, W, B, pad, dil, dil2, terms = key
+    return "g%d,b%d|%d,%d,%d,%d|%d,%d,%d,%d,%d,%d" % (gate, terms, pc.cout, pc.cin, pc.kh, pc.kw, H, W, B, pad, dil, dil2)
+
+
+# One conv2d / conv_gate call as its chooser and its launch tail see it: the library, the ConvParams ``p`` of the launch,
+# the layer, its launch-shape key, geom = the arguments of _conv_cfg after pc, the terms of the precision mode, the fp32
+# input (x: a Slice, None when the input exists in record form only; x2), the shared SplitTensor ``xs`` and the record
+# output ``xs_out`` with their channel offsets, and small: only the _small_footprint split candidates are tried.
+_ConvCall = collections.namedtuple("_ConvCall", "lib p pc key geom terms x x2 xs xs_coff xs_out xs_out_coff small")
+
+
+def _split_cands(call):
+    """The split-bf16 configurations the library accepts for this call, best guess first."""
+    Hout, Wout, B = call.geom[:3]
+    cands = [c for c in _bf16_candidates(call.pc, Hout, Wout, B, call.pc.kh * call.pc.kw, call.terms)
+             if _cfg_ok(call.lib, call.p, c)]
+    return _small_footprint(cands) if call.small else cands
+
+
+def _pinned_cands(call):
+    cands = _split_cands(call)
+    if not cands:
+        raise _abi.CoddHipError("no split-bf16 launch configuration for %sconv %dx%d %d->%d" % (
+            "gate " if call.p.gate else "", call.pc.kh, call.pc.kw, call.pc.cin, call.pc.cout))
+    return cands
+
+
+def _heuristic(call):
+    return _conv_cfg(call.pc, *call.geom)
+
+
+def _tune_pinned(call, cands):
+    """Time the candidates on the real split input / output tensors (into a scratch ``out``: in-place gates are safe)."""
+    keep = None if call.x is None else _make_split(call.lib, call.p, call.x, call.x2, cands)  # noqa: F841
+    if call.x is None:
+        _attach_xs(call.p, call.xs, call.xs_coff)
+    if call.xs_out is not None:
+        _attach_xso(call.p, call.xs_out, call.xs_out_coff)
+    return _autotune_b(call.lib, call.p, call.pc, cands, None, None)[0]
+
+
+def _untimed_pinned(call, cands):
+    """The configuration this layer was tuned to in its plain form (the signature without "|split") if that is a split
+    one, else the first candidate."""
+    plain = TUNE_DB.get(_plain_sig(call.pc, call.key[:10])) if _AUTOTUNE and not _CORESIDENT else None
+    return tuple(plain) if plain is not None and decode_cfg(plain).layout == 2 else cands[0]
+
+
+def _tune_choice(call, cands):
+    """Measure: the best split-bf16 configuration (incl. its re-layout pass) against the best exact-fp32 one -- small or
+    large-map layers can be faster (and are more exact) on the fp32 kernels."""
+    lib, p, pc = call.lib, call.p, call.pc
+    f32cfg, t32 = _autotune(lib, p, pc, _heuristic(call) + (pc.mb, 0))
+    p.terms = call.terms
+    bcfg, tb = (None, float("inf"))
+    if cands:
+        keep = _make_split(lib, p, call.x, call.x2, cands)  # noqa: F841 one split input serving every candidate
+        bcfg, tb = _autotune_b(lib, p, pc, cands, call.x, call.x2)
+    cfg = bcfg if tb < t32 else f32cfg
+    AUTOTUNE_LOG.append(("choice %dx%d %d->%d out %dx%d" % (pc.kh, pc.kw, pc.cin, pc.cout, call.geom[0], call.geom[1]),
+                         f32cfg, t32 * 1e3, cfg, min(tb, t32) * 1e3))
+    return cfg
+
+
+# How a launch shape met for the first time gets its configuration (_pick_cfg): the candidates, how they are timed when
+# autotuning, the pick when they are not, the signature format, and kept: the pick stays in pc.tuned even when it was
+# made untimed while capturing with autotune on.
+_Chooser = collections.namedtuple("_Chooser", "candidates tune untimed sig kept")
+_PINNED = _Chooser(_pinned_cands, _tune_pinned, _untimed_pinned, _plain_sig, True)  # input or output in record form
+_CHOICE = _Chooser(_split_cands, _tune_choice,  # split-bf16 or exact fp32
+                   lambda call, cands: cands[0] if cands else _heuristic(call) + (call.pc.mb, 0), _plain_sig, False)
+_FP32 = _Chooser(lambda call: [_heuristic(call)],
+                 lambda call, cands: _autotune(call.lib, call.p, call.pc, cands[0] + (call.pc.mb, 0))[0],
+                 lambda call, cands: cands[0], _plain_sig, False)
+_GATE = _Chooser(_pinned_cands, _tune_pinned, lambda call, cands: cands[0], _gate_sig, False)
+
+
+def _choose(call, how):
+    bind = functools.partial
+    cfg = _pick_cfg(call.lib, call.p, call.pc, call.key, how.sig(call.pc, call.key), bind(how.candidates, call),
+                    bind(how.tune, call), bind(how.untimed, call))
+    if how.kept:
+        call.pc.tuned[call.key] = cfg
+    return cfg
+
+
+def _launch_split(call, cfg, what="codd_conv2d"):
+    """Launch the call on the split-bf16 kernel with configuration ``cfg``: from the shared SplitTensor when it is one of
+    this call's input; where there is none, or the library finds that it does not fit this configuration's tiles (rc -1),
+    from a private re-layout of the fp32 input -- which an input in record form only does not have."""
+    lib, p, pc, xs = call.lib, call.p, call.pc, call.xs
+    if call.xs_out is not None:
+        _attach_xso(p, call.xs_out, call.xs_out_coff)
+    if (xs is not None and xs.terms == call.terms and (xs.B, xs.H, xs.W) == (p.B, p.Hin, p.Win) and call.xs_coff % 8 == 0
+            and call.xs_coff + pc.cin <= max(xs.C, 8 * xs.c8 if call.x is None else 0)):
+        _attach_xs(p, xs, call.xs_coff)
+        _set_cfg(p, cfg, pc)
+        rc = _launch_conv(lib, p, _stream())
+        if rc == 0:
+            return
+        if rc != -1 or call.x is None:
+            _abi.check(rc, what)
+    elif call.x is None:
+        raise _abi.CoddHipError("%s: the split input is not one of this convolution's input" % what)
+    keep = _make_split(lib, p, call.x, call.x2, [cfg])  # noqa: F841 (alive until the launch below is enqueued)
+    _set_cfg(p, cfg, pc)
+    _abi.check(_launch_conv(lib, p, _stream()), what)
+
+
 def conv2d(x, pc, x2=None, stride=1, pad=0, dil=1, act="none", res1=None, res2=None, post=None,
            out=None, pad_tl=None, out_hw=None, xs=None, xs_coff=0, xs_out=None, xs_out_coff=0):
     """act(conv(cat[x, x2]) + bias + res1 + res2) + post  ->  out (tensor or Slice).
@@ -476,139 +636,51 @@ def conv2d(x, pc, x2=None, stride=1, pad=0, dil=1, act="none", res1=None, res2=N
     channel offset ``xs_out_coff`` instead of an fp32 tensor, and return it -- the next convolution then needs no
     re-layout pass.  Both options pin the layer to the split-bf16 kernel."""
     lib = _abi.load()
-    force_split = (x is None) or (xs_out is not None)
+    pinned = (x is None) or (xs_out is not None)
     if x is None:
         assert xs is not None and x2 is None and xs_coff % 8 == 0
-        _require_gpu(xs.buf)
+        xsl, src = None, xs.buf
         B, C0, Hin, Win = xs.B, pc.cin, xs.H, xs.W
-        xsl = None
-        dev_ = xs.buf.device
     else:
         xsl = _as_slice(x)
-        _require_gpu(xsl.buf)
+        src = xsl.buf
         B, C0, Hin, Win = xsl.shape
-        dev_ = xsl.buf.device
+    _require_gpu(src)
     C1 = 0
     if x2 is not None:
         x2s = _as_slice(x2)
         C1 = x2s.c
         assert x2s.shape[2:] == (Hin, Win)
     assert C0 + C1 == pc.cin, (C0, C1, pc.cin)
-    sy, sx = (stride, stride) if isinstance(stride, int) else stride
-    dy, dx = (dil, dil) if isinstance(dil, int) else dil
-    if pad_tl is None:
-        pt, pl = (pad, pad) if isinstance(pad, int) else pad
-        pb_, pr_ = pt, pl
-    else:
-        pt, pl, pb_, pr_ = pad_tl
-    if pc.deconv:
-        Hout, Wout = Hin, Win
-    elif out_hw is not None:
-        Hout, Wout = out_hw
-    else:
-        Hout = (Hin + pt + pb_ - dy * (pc.kh - 1) - 1) // sy + 1
-        Wout = (Win + pl + pr_ - dx * (pc.kw - 1) - 1) // sx + 1
-    up = 2 if pc.deconv else 1
+    (sy, sx), (pt, pl), (dy, dx), (Hout, Wout, up) = _conv_geometry(pc, Hin, Win, stride, pad, dil, pad_tl, out_hw)
     terms = _TERMS.get(CONV_PRECISION, 0)
-    if force_split and not terms:
+    if pinned and not terms:
         raise _abi.CoddHipError("split-form convolution inputs / outputs need the 'split' or 'bf16' conv precision")
+    p = _conv_params(pc, B, C0, C1, Hin, Win, Hout, Wout, (sy, sx), (pt, pl), (dy, dx), act)
+    p.in0, p.in1 = _view(xsl), _view(x2)
+    p.res1, p.res2, p.post = _view(res1), _view(res2), _view(post)
+    p.terms = terms
     if xs_out is None:
         if out is None:
-            out = torch.empty(B, pc.cout, Hout * up, Wout * up, device=dev_, dtype=torch.float32)
+            out = torch.empty(B, pc.cout, Hout * up, Wout * up, device=src.device, dtype=torch.float32)
         os_ = _as_slice(out)
         assert os_.shape == (B, pc.cout, Hout * up, Wout * up), (os_.shape, (B, pc.cout, Hout * up, Wout * up))
+        p.out, p.out_ctot, p.out_coff = os_.buf.data_ptr(), os_.buf.shape[1], os_.coff
     else:
         assert (xs_out.B, xs_out.H, xs_out.W) == (B, Hout, Wout) and xs_out.terms == terms and xs_out_coff % 8 == 0
         assert xs_out_coff + pc.cout <= 8 * xs_out.c8 and not pc.deconv and res1 is None and res2 is None and post is None
-        os_ = None
-    key = (Hout, Wout, B, sy, sx, dy, dx, pl, C1 > 0, terms) + (("split",) if force_split else ()) + (
-        ("co",) if _CORESIDENT and terms else ())
-    p = _conv_params(pc, B, C0, C1, Hin, Win, Hout, Wout, (sy, sx), (pt, pl), (dy, dx), act)
-    p.in0 = _view(xsl)
-    p.in1 = _view(x2)
-    p.res1, p.res2, p.post = _view(res1), _view(res2), _view(post)
-    if os_ is not None:
-        p.out, p.out_ctot, p.out_coff = os_.buf.data_ptr(), os_.buf.shape[1], os_.coff
-    p.terms = terms
-
-    cfg = pc.tuned.get(key)
+        out = xs_out
+    geom = (Hout, Wout, B, sy, sx, dy, dx, pl)
+    call = _ConvCall(lib, p, pc, _plain_key(geom, C1 > 0, terms, pinned), geom, terms, xsl, x2, xs, xs_coff, xs_out,
+                     xs_out_coff, _CORESIDENT)
+    cfg = pc.tuned.get(call.key)
     if cfg is None:
-        sig = ("b%d|" % terms if terms else "") + "%d,%d,%d,%d,%d,%d|" % (
-            pc.cout_eff, pc.cin, pc.kh, pc.kw, pc.mb, int(pc.deconv)) + ",".join(str(int(v)) for v in key[:9]) + (
-                "|split" if force_split else "") + ("|co" if _CORESIDENT and terms else "")
-        co = _small_footprint if _CORESIDENT else (lambda c: c)
-
-        def split_cands():
-            return co([c for c in _bf16_candidates(pc, Hout, Wout, B, pc.kh * pc.kw, terms) if _cfg_ok(lib, p, c)])
-
-        def heuristic():
-            return _conv_cfg(pc, Hout, Wout, B, sy, sx, dy, dx, pl)
-
-        if force_split:
-            # pinned to the split-bf16 kernel: the configuration this layer was tuned to in its plain form if that is
-            # a split one, else the first candidate the library accepts
-            def pinned_cands():
-                cands = split_cands()
-                if not cands:
-                    raise _abi.CoddHipError("no split-bf16 launch configuration for conv %dx%d %d->%d" % (
-                        pc.kh, pc.kw, pc.cin, pc.cout))
-                return cands
-
-            def tune_pinned(cands):  # time the candidates on the real split input / output tensors
-                keep = None if x is None else _make_split(lib, p, xsl, x2, cands)  # noqa: F841
-                if x is None:
-                    _attach_xs(p, xs, xs_coff)
-                if xs_out is not None:
-                    _attach_xso(p, xs_out, xs_out_coff)
-                return _autotune_b(lib, p, pc, cands, None, None)[0]
-
-            def untimed(cands):
-                plain = TUNE_DB.get(sig[:-6]) if _AUTOTUNE and not _CORESIDENT else None
-                return tuple(plain) if plain is not None and decode_cfg(plain).layout == 2 else cands[0]
-
-            # (kept in pc.tuned even when picked while capturing with autotune on)
-            cfg = pc.tuned[key] = _pick_cfg(lib, p, pc, key, sig, pinned_cands, tune_pinned, untimed)
-        elif terms:
-            def tune_choice(cands):
-                # measure: best split-bf16 configuration (incl. its re-layout pass) against the best exact-fp32 one --
-                # small or large-map layers can be faster (and are more exact) on the fp32 kernels
-                f32cfg, t32 = _autotune(lib, p, pc, heuristic() + (pc.mb, 0))
-                p.terms = terms
-                bcfg, tb = (None, float("inf"))
-                if cands:
-                    keep = _make_split(lib, p, xsl, x2, cands)  # noqa: F841 one split input serving every candidate
-                    bcfg, tb = _autotune_b(lib, p, pc, cands, xsl, x2)
-                cfg = bcfg if tb < t32 else f32cfg
-                AUTOTUNE_LOG.append(("choice %dx%d %d->%d out %dx%d" % (pc.kh, pc.kw, pc.cin, pc.cout, Hout, Wout),
-                                     f32cfg, t32 * 1e3, cfg, min(tb, t32) * 1e3))
-                return cfg
-
-            cfg = _pick_cfg(lib, p, pc, key, sig, split_cands, tune_choice,
-                            lambda cands: cands[0] if cands else heuristic() + (pc.mb, 0))
-        else:
-            cfg = _pick_cfg(lib, p, pc, key, sig, lambda: [heuristic()],
-                            lambda cands: _autotune(lib, p, pc, cands[0] + (pc.mb, 0))[0])
-
+        cfg = _choose(call, _PINNED if pinned else _CHOICE if terms else _FP32)
     if decode_cfg(cfg).layout == 2:  # split-bf16 / bf16 kernel
-        keep = None
-        if xs_out is not None:
-            _attach_xso(p, xs_out, xs_out_coff)
-            out = xs_out
-        if (xs is not None and xs.terms == terms and (xs.B, xs.H, xs.W) == (B, Hin, Win) and xs_coff % 8 == 0 and
-                xs_coff + pc.cin <= max(xs.C, 8 * xs.c8 if x is None else 0)):
-            _attach_xs(p, xs, xs_coff)
-            _set_cfg(p, cfg, pc)
-            rc = _launch_conv(lib, p, _stream())
-            if rc == 0:
-                return out
-            if rc != -1 or x is None:  # -1: the shared tensor does not fit this configuration's tiles -> private re-layout below
-                _abi.check(rc, "codd_conv2d")
-        keep = _make_split(lib, p, xsl, x2, [cfg])  # noqa: F841 (alive until the launch below is enqueued)
-        _set_cfg(p, cfg, pc)
-        _abi.check(_launch_conv(lib, p, _stream()), "codd_conv2d")
+        _launch_split(call, cfg)
         return out
     _set_cfg(p, cfg, pc)
-    heur = (key, (Hout, Wout, B, sy, sx, dy, dx, pl))
+    heur = (call.key, geom)
     if _DEFERRED is not None and p.layout == 1 and p.npb == 1 and p.nw == 4 and p.mb == 1:
         # inside ``with deferred_convs():`` -- recorded, launched on exit together with its independent neighbours
         _DEFERRED.append((ConvParams.from_buffer_copy(p), (x, x2, res1, res2, post, out), pc, heur))
@@ -739,11 +811,9 @@ def conv2d_multi(jobs):
         j = jobs[idx]
         x, pc = j["x"], j["pc"]
         B, C0, Hin, Win = x.shape
-        st, pad = j.get("stride", 1), j.get("pad", 0)
-        Hout = (Hin + 2 * pad - (pc.kh - 1) - 1) // st + 1
-        Wout = (Win + 2 * pad - (pc.kw - 1) - 1) // st + 1
+        stride, pad, dil, (Hout, Wout, _) = _conv_geometry(pc, Hin, Win, j.get("stride", 1), j.get("pad", 0))
         out = outs[idx] = torch.empty(B, pc.cout, Hout, Wout, device=x.device, dtype=torch.float32)
-        p = _conv_params(pc, B, C0, 0, Hin, Win, Hout, Wout, (st, st), (pad, pad), (1, 1), j.get("act", "none"))
+        p = _conv_params(pc, B, C0, 0, Hin, Win, Hout, Wout, stride, pad, dil, j.get("act", "none"))
         p.in0, p.res1 = _view(x), _view(j.get("res1"))
         p.out, p.out_ctot, p.out_coff = out.data_ptr(), pc.cout, 0
         _set_cfg(p, (1, 4, 32 if pc.cin > 16 else 16, 1, 1), pc)
@@ -818,32 +888,17 @@ def conv_gate(pc, xs, gate, pad=0, dil=1, dil2=0, out=None, out_coff=0, res1=Non
     for name, t in (("res1", res1), ("res2", res2), ("post", post)):
         if t is not None:
             setattr(p, name, t.view())
-    _attach_xs(p, xs, xs_coff)
-    if xs_out is not None:
-        _attach_xso(p, xs_out, 0)
-    key = ("gate", gate, H, W, B, pad, dil, dil2, terms)
-    cfg = pc.tuned.get(key)
+    # small (gate 1): the z|r convolution runs BESIDE the VALU-only Gauss-Newton builder (BasicUpdateBlock.zr_convs): a
+    # stand-alone timing would pick 12-wave workgroups, whose ~450 registers per SIMD leave the builder no room on the
+    # same CU; 8-wave workgroups (2 waves per SIMD, ~106 registers each) co-reside with two builder waves per SIMD.
+    # Measured in the frame: 93.2-93.5 against 91.7-92.1 frames/s (profiles/r03_ab_runs.log, "zc"); the isolated timing
+    # then only chooses among those.
+    call = _ConvCall(lib, p, pc, _gate_key(gate, H, W, B, pad, dil, dil2, terms), (H, W, B, 1, 1, dil, dil, pad), terms,
+                     None, None, xs, xs_coff, xs_out, 0, gate == 1)
+    cfg = pc.tuned.get(call.key)
     if cfg is None:
-        sig = "g%d,b%d|%d,%d,%d,%d|%d,%d,%d,%d,%d,%d" % (gate, terms, pc.cout, pc.cin, pc.kh, pc.kw, H, W, B, pad, dil, dil2)
-
-        def candidates():
-            cands = [c for c in _bf16_candidates(pc, H, W, B, pc.kh * pc.kw, terms) if _cfg_ok(lib, p, c)]
-            if gate == 1:
-                # the z|r convolution runs BESIDE the VALU-only Gauss-Newton builder (BasicUpdateBlock.zr_convs): a
-                # stand-alone timing would pick 12-wave workgroups, whose ~450 registers per SIMD leave the builder
-                # no room on the same CU; 8-wave workgroups (2 waves per SIMD, ~106 registers each) co-reside with
-                # two builder waves per SIMD.  Measured in the frame: 93.2-93.5 against 91.7-92.1 frames/s
-                # (tools/zr_cfg_sweep.sh); the isolated timing then only chooses among those.
-                cands = _small_footprint(cands)
-            if not cands:
-                raise _abi.CoddHipError("no split-bf16 launch configuration for gate conv %dx%d %d->%d" % (
-                    pc.kh, pc.kw, pc.cin, pc.cout))
-            return cands
-
-        # (times into a scratch ``out``: in-place gates are safe)
-        cfg = _pick_cfg(lib, p, pc, key, sig, candidates, lambda cands: _autotune_b(lib, p, pc, cands, None, None)[0])
-    _set_cfg(p, cfg, pc)
-    _abi.check(_launch_conv(lib, p, _stream()), "codd_conv2d (gate %d)" % gate)
+        cfg = _choose(call, _GATE)
+    _launch_split(call, cfg, "codd_conv2d (gate %d)" % gate)
     return out
 
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CODD_ABI_VERSION 12
+#define CODD_ABI_VERSION 13
 
 #define CODD_OK 0
 #define CODD_EINVAL (-1)
@@ -186,10 +186,18 @@ int codd_conv2d(const codd_conv_params* p, void* stream);
  * 1 | 2): the resolution branches of an mmseg HRModule (configs/models/codd.py:44-74) are launch-bound ~10 us layers
  * that do not depend on each other.  CODD_EUNSUPPORTED when a job does not fit that class (launch them one by one). */
 int codd_conv2d_multi(const codd_conv_params* p, int n, void* stream);
-/* layout 2 only: CODD_OK if codd_conv2d would accept this launch configuration (tile, chunk depth, wave grid: LDS
- * and register-staging limits of the instantiated kernels), CODD_EUNSUPPORTED otherwise.  Launches nothing and reads
- * no pointer field: callers probe candidate configurations before packing weights for them. */
+/* Dry runs (ABI v13 for layouts 0 and 1): they launch nothing and read no pointer field -- the pointer checks of
+ * codd_conv2d are skipped and its alignment-dependent choices see null pointers, i.e. aligned operands -- so callers probe
+ * candidate configurations before packing weights for them.
+ *   codd_conv2d_lds_bytes  the dynamic LDS bytes of the launch codd_conv2d would make with this configuration (tile,
+ *                          chunk depth, wave grid), or the negative CODD_E* code with which it would refuse it (LDS and
+ *                          register-staging limits of the instantiated kernels)
+ *   codd_conv2d_check      CODD_OK where that is >= 0, else that code */
+long long codd_conv2d_lds_bytes(const codd_conv_params* p);
 int codd_conv2d_check(const codd_conv_params* p);
+/* The layout-2 kernels this build instantiates: writes up to `cap` quintuples (pgw, cgw, A, B, ksplit) -- A = pixel units
+ * per wave row group (nw * npb = pgw * A), B = mb / cgw -- in dispatch order and returns their number. */
+int codd_conv2d_bf16_instantiations(int* out, int cap);
 
 /* quad layout (layout = 1): four input channels innermost, [cog][chunk][tap][c/4][co][4] */
 long long codd_conv2d_packed_size_quad(int Cout, int Cin, int kh, int kw, int mb, int ck);

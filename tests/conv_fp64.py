@@ -69,7 +69,8 @@ Layer = collections.namedtuple("Layer", "cout_eff cin kh kw deconv sy sx dy dx p
 
 
 def parse_sig(sig, cfg=()):
-    """One of the three signature forms of the tune db -> Entry:
+    """One of the three signature forms of the tune db (built by ops._plain_sig / ops._gate_sig; the comment above
+    ops._plain_key states them) -> Entry:
         cout_eff,cin,kh,kw,mb,deconv|Hout,Wout,B,sy,sx,dy,dx,pl,two                      (precision fp32)
         b<terms>|cout_eff,cin,kh,kw,mb,deconv|Hout,Wout,B,sy,sx,dy,dx,pl,two[|split][|co]
         g<gate>,b<terms>|cout,cin,kh,kw|H,W,B,pad,dil,dil2"""

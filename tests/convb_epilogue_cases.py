@@ -53,6 +53,18 @@ def xname(X):
     return "x%d_%d_%d_%d_k%d" % X
 
 
+def header_convb_all():
+    """The expansion of CONVB_ALL parsed from conv_bf16_kernel.h: [(PGW, CGW, A, B, KS)] in its order."""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = open(os.path.join(root, "codd_amd", "csrc", "conv_bf16_kernel.h")).read()
+    groups = dict(re.findall(r"#define CONVB_GROUP_(\w)\(X\) (.*)", src))
+    listed = re.search(r"#define CONVB_ALL\(X\)(.*?)\n#define", src, re.S).group(1)
+    return [tuple(int(v) for v in x) for gname in re.findall(r"CONVB_GROUP_(\w)\(X\)", listed)
+            for x in re.findall(r"X\((\d+), (\d+), (\d+), (\d+), (\d+)\)", groups[gname])]
+
+
 def cfg_of(X, terms):
     """The stored launch configuration (xb, th, ck, mb, 2, pgw, cgw, terms, ksplit) that runs instantiation X: tiles of
     th x 32 pixels = PGW * A pixel units, mb = B * CGW channel blocks."""

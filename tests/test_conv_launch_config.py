@@ -61,7 +61,8 @@ def test_malformed_configurations_are_refused():
 
 
 def _layer(sig):
-    """ConvParams of the layer a tune-db signature describes (only what codd_conv2d_check reads)."""
+    """ConvParams of the layer a tune-db signature describes (only what codd_conv2d_check reads); the signature formats
+    are stated once, in the comment above ops._plain_key."""
     p = _abi.ConvParams()
     head, w, shape = sig.split("|")[:3]
     if head.startswith("g"):  # gate epilogue: "g<gate>,b<terms>|cout,cin,kh,kw|H,W,B,pad,dil,dil2"
@@ -98,3 +99,22 @@ def test_shipped_tune_db_decodes_and_its_split_entries_are_accepted():
         ops._set_cfg(p, cfg)
         assert lib.codd_conv2d_check(C.byref(p)) == 0, (sig, cfg)
     assert n_split > 200, n_split
+
+
+def test_library_instantiations_are_the_headers_and_tiles_match():
+    """codd_conv2d_bf16_instantiations (what ops._B_INST reads) is the CONVB_ALL expansion of conv_bf16_kernel.h, and
+    ops._B_TILES lists tiles for exactly the pixel-unit counts (pgw * A) of those instantiations."""
+    from convb_epilogue_cases import header_convb_all
+    lib = _abi.load()
+    n = lib.codd_conv2d_bf16_instantiations(None, 0)
+    flat = (C.c_int * (5 * n))()
+    assert lib.codd_conv2d_bf16_instantiations(flat, n) == n
+    got = [tuple(flat[5 * i:5 * i + 5]) for i in range(n)]
+    assert got == header_convb_all() and len(set(got)) == n > 0
+    assert list(ops._B_INST) == got
+    short = (C.c_int * 10)(*([-7] * 10))  # cap: only whole quintuples below it are written
+    assert lib.codd_conv2d_bf16_instantiations(short, 1) == n and list(short) == list(got[0]) + [-7] * 5
+    assert set(ops._B_TILES) == {pgw * a for (pgw, _, a, _, _) in got}
+    for units, tiles in ops._B_TILES.items():  # the dispatch runs a tile of th * xb units on A = ceil(th * xb / pgw)
+        grids = {(pgw, a) for (pgw, _, a, _, _) in got if pgw * a == units}
+        assert tiles and all(xb in (1, 2) and any(-(-th * xb // pgw) == a for (pgw, a) in grids) for (th, xb) in tiles), (units, tiles)

@@ -10,9 +10,6 @@ the written bytes per launch (tools/parent_bits.py made it on the GPU with that 
 * a bias 4 bytes off a 16-byte boundary is refused with CODD_EINVAL;
 * the case list reaches every branch (no GPU needed), and the fixture is not from the library under test.
 A key missing from the fixture, or one the fixture has and the tree does not, fails."""
-import os
-import re
-
 import pytest
 
 import convb_epilogue_cases as BC
@@ -35,11 +32,7 @@ def test_cases_reach_every_branch():
     """No GPU needed.  The case list names exactly the instantiations of CONVB_ALL in the header, each in the four operand
     formats on the three maps; the maps hold partial tiles in both axes, a unit valid for a few lanes only and empty
     units; the record cases take the 16-byte and the per-element bias path, the gates all three tile kinds of gate 2."""
-    src = open(os.path.join(P.ROOT, "codd_amd", "csrc", "conv_bf16_kernel.h")).read()
-    groups = dict(re.findall(r"#define CONVB_GROUP_(\w)\(X\) (.*)", src))
-    listed = re.search(r"#define CONVB_ALL\(X\)(.*?)\n#define", src, re.S).group(1)
-    header = [tuple(int(v) for v in x) for gname in re.findall(r"CONVB_GROUP_(\w)\(X\)", listed)
-              for x in re.findall(r"X\((\d+), (\d+), (\d+), (\d+), (\d+)\)", groups[gname])]
+    header = BC.header_convb_all()
     assert header == list(BC.CONVB_ALL) and len(set(header)) == 16
     got = {(X, (H, W), t, n) for (_, X, H, W, t, n) in CASES}
     for X in BC.CONVB_ALL:

@@ -6,7 +6,7 @@ import pytest
 
 import parent_bits as P
 
-NAMES = ("conv_epilogue", "conv_epilogue_vec", "convb_epilogue", "load_chain", "ingest")
+NAMES = ("conv_epilogue", "conv_epilogue_vec", "convb_epilogue", "load_chain", "ingest", "conv_plan")
 
 
 @pytest.mark.parametrize("name", NAMES)
