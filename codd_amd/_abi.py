@@ -57,6 +57,11 @@ class CalibView(C.Structure):  # codd_calib_view
                 ("dist", C.c_double * 8), ("model", C.c_int)]
 
 
+class AlignView(C.Structure):  # codd_align_view
+    _fields_ = [("R", C.c_double * 9), ("T", C.c_double * 3), ("K", C.c_double * 4), ("dist", C.c_double * 8),
+                ("r2_max", C.c_double), ("model", C.c_int)]
+
+
 _i, _f, _p, _ll = C.c_int, C.c_float, C.c_void_p, C.c_longlong
 
 # name -> (restype, argtypes); must list every function declared in include/codd_hip.h
@@ -138,6 +143,7 @@ SIGNATURES = {
     "codd_ego_motion_scratch": (_ll, [_i, _i]),
     "codd_ego_motion": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _i, _p, _ll, _p, _p, _p, _p]),
     "codd_export_confidence": (_i, [_p, _p, _p, _i, _i, _i, _i, c_float_p, _f, _f, _p, _p, _p]),
+    "codd_align_depth": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, C.POINTER(AlignView), _i, _i, _i, _p, _p, _p]),
 }
 
 ABI_VERSION = 13  # CODD_ABI_VERSION of include/codd_hip.h

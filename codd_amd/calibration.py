@@ -9,7 +9,12 @@ stated once in include/codd_hip.h (THE MAP FUNCTION) and evaluated on the GPU (o
 arrays, ops.ingest_calibrated evaluates it inside the ingest launch); ``Rectification.source_points`` is the same
 function in fp64 for use on the host.
 
-Files: ``.json`` and ``.npz`` with the plain keys listed in INTEGRATION.md ("Rectification from a calibration").
+``AlignTarget`` describes one more calibrated camera -- a physical camera of the rig or a separate colour camera -- to
+which ``LiveSession(align_to=)`` registers the depth map (ops.align_depth); ``fold_radius2`` and ``auto_footprint`` derive
+the two parameters of that launch the user does not have to think about.
+
+Files: ``.json`` and ``.npz`` with the plain keys listed in INTEGRATION.md ("Rectification from a calibration", "Depth on
+another camera's grid").
 """
 import json
 import os
@@ -314,6 +319,178 @@ class StereoCalibration:
 
     def save(self, path):
         _save(self.to_dict(), path)
+
+
+# ---- another calibrated camera to register the depth map to -------------------------------------------------
+R2_CAP = 1e6  # fold_radius2 of a lens that never folds: a radius of 1000 focal lengths, 89.94 degrees off the axis
+FOOTPRINT_GRID, MAX_FOOTPRINT = 33, 4  # (CODD_ALIGN_MAX_FOOTPRINT of include/codd_hip.h)
+
+
+def fold_radius2(camera, samples=4096):
+    """The ``r2_max`` of codd_align_depth for ``camera``: the squared normalised radius up to which the lens model is
+    monotonic.  The distorted radius of a point at radius r -- brown: r (1 + k1 r^2 + k2 r^4 + k3 r^6) / (1 + k4 r^2 + k5 r^4
+    + k6 r^6), the radial part; fisheye: theta_d(atan r) -- is scanned outward in fp64 at r = tan(theta), theta uniform in
+    (0, atan sqrt(R2_CAP)]; the answer is r^2 at the last sample before it first stops increasing (a polynomial with a
+    negative leading coefficient turns back there and would project far-off points into the image), or ``R2_CAP``."""
+    th = np.arctan(np.sqrt(R2_CAP)) * np.arange(0, samples + 1, dtype=np.float64) / samples
+    r = np.tan(th)
+    r2 = r * r
+    with np.errstate(all="ignore"):
+        if camera.model == "brown":
+            k1, k2, _, _, k3, k4, k5, k6 = camera.dist8
+            rd = r * (1 + r2 * (k1 + r2 * (k2 + r2 * k3))) / (1 + r2 * (k4 + r2 * (k5 + r2 * k6)))
+        else:
+            k1, k2, k3, k4 = camera.dist8[:4]
+            t2 = th * th
+            rd = th * (1 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))))
+        rising = np.diff(rd) > 0  # (False for a NaN or an infinity on either side)
+    stop = np.flatnonzero(~rising)
+    if stop.size == 0:
+        return R2_CAP
+    if stop[0] == 0:
+        raise ValueError(f"camera: the lens model does not increase from the centre on ({camera!r})")
+    return float(min(r2[stop[0]], R2_CAP))
+
+
+def auto_footprint(R, camera, shape, intrinsics, r2_max=None):
+    """The footprint ``k`` that leaves no hole lines: ``clamp(ceil(m - 1e-3), 1, 4)``, ``m`` the largest ``|dsx/du|`` or
+    ``|dsy/dv|`` of the map rectified pixel -> target position for points at infinity (``X_t = R X``: no translation), by
+    central differences of half a pixel either way on a 33 x 33 grid over the rectified image of ``shape`` (h, w) with
+    ``intrinsics`` (f', f', cx', cy').  Positions behind the target or beyond ``r2_max`` take no part; none at all: 1."""
+    R = _rotation(R, "R")
+    h, w = _size(shape, "shape")
+    f, _, cx, cy = (float(v) for v in intrinsics)
+    r2_max = fold_radius2(camera) if r2_max is None else float(r2_max)
+    vv, uu = np.meshgrid(np.linspace(0.0, h - 1.0, FOOTPRINT_GRID), np.linspace(0.0, w - 1.0, FOOTPRINT_GRID), indexing="ij")
+
+    def at(u, v):
+        X = np.stack([(u - cx) / f, (v - cy) / f, np.ones_like(u)])
+        Xt = np.tensordot(R, X, 1)
+        ok = Xt[2] > 0
+        z = np.where(ok, Xt[2], 1.0)
+        x, y = Xt[0] / z, Xt[1] / z
+        ok &= x * x + y * y <= r2_max
+        sx, sy = camera.distort(np.where(ok, x, 0.0), np.where(ok, y, 0.0))
+        return np.where(ok, sx, np.nan), np.where(ok, sy, np.nan)
+
+    du = np.abs(at(uu + 0.5, vv)[0] - at(uu - 0.5, vv)[0])
+    dv = np.abs(at(uu, vv + 0.5)[1] - at(uu, vv - 0.5)[1])
+    m = np.concatenate([du[np.isfinite(du)], dv[np.isfinite(dv)]])
+    if m.size == 0:
+        return 1
+    return int(min(max(np.ceil(m.max() - 1e-3), 1), MAX_FOOTPRINT))
+
+
+class AlignTarget:
+    """A calibrated camera to register the session's depth map to (``LiveSession(align_to=)``): ``camera`` its
+    ``CameraModel`` and its pose ``X_target = R X_left + T``, the convention of ``cv2.stereoCalibrate`` between the left
+    camera and this one.  ``X_left`` is the PHYSICAL left camera when the session has ``calibration=`` and the rectified
+    left camera (the only one there is) otherwise; ``T`` is in the unit of the rig's baseline.  ``rectified=True`` says
+    that the pose refers to the rectified left camera although the session has a calibration: what ``of_rig`` builds."""
+
+    def __init__(self, camera, R=None, T=None, rectified=False):
+        if not isinstance(camera, CameraModel):
+            raise ValueError(f"camera: a CameraModel is expected, got {type(camera).__name__}")
+        self.camera = camera
+        self.R = _rotation(np.eye(3) if R is None else R, "R")
+        self.T = _finite(np.zeros(3) if T is None else T, "T").reshape(-1)
+        if self.T.shape != (3,):
+            raise ValueError(f"T: 3 entries expected, got {self.T.size}")
+        self.rectified = bool(rectified)
+
+    @classmethod
+    def of_rig(cls, rect, side):
+        """The rig's own ``side`` ("left" or "right") physical camera as a target, from a ``Rectification`` alone: relative
+        to the rectified left camera, left: ``R = R1^T, T = 0``; right: ``R = R2^T, T = -baseline R2^T e_x``."""
+        if not isinstance(rect, Rectification):
+            raise ValueError(f"rect: a Rectification is expected, got {type(rect).__name__}")
+        if side not in ("left", "right"):
+            raise ValueError(f"side: 'left' or 'right' expected, got {side!r}")
+        if side == "left":
+            return cls(rect.views[0].camera, rect.R1.T, np.zeros(3), rectified=True)
+        Rt = rect.R2.T
+        return cls(rect.views[1].camera, Rt, -rect.baseline * Rt[:, 0], rectified=True)
+
+    def pose_from(self, rect=None):
+        """``(R, T)`` with ``X_target = R X_rect + T``, ``X_rect`` in the rectified left camera of ``rect`` (None: the
+        session has no calibration, or the target is ``rectified``: its own pose)."""
+        if rect is None or self.rectified:
+            return self.R.copy(), self.T.copy()
+        return self.R @ rect.R1.T, self.T.copy()  # X_left = R1^T X_rect
+
+    def to_dict(self):
+        return dict(size=list(self.camera.size), camera=self.camera.to_dict(), R=self.R.tolist(), T=self.T.tolist(),
+                    rectified=self.rectified)
+
+    def save(self, path):
+        path = os.fspath(path)
+        ext = os.path.splitext(path)[1].lower()
+        d = self.to_dict()
+        if ext == ".json":
+            with open(path, "w") as f:
+                json.dump(d, f, indent=1)
+        elif ext == ".npz":
+            cam = d["camera"]
+            with open(path, "wb") as f:  # (np.savez appends .npz to a name, not to a file object)
+                np.savez(f, size=np.asarray(d["size"], np.int64), R=self.R, T=self.T, rectified=np.asarray(self.rectified),
+                         camera_K=np.asarray(cam["K"], np.float64), camera_model=np.asarray(cam["model"]),
+                         camera_dist=np.asarray(cam["dist"], np.float64))
+        else:
+            raise ValueError(f"align target file: .json or .npz expected, got {path!r}")
+
+    @classmethod
+    def from_dict(cls, d):
+        missing = [k for k in ("size", "camera", "R", "T") if k not in d]
+        if missing:
+            raise ValueError(f"align target file: missing keys {missing}")
+        size = tuple(int(v) for v in np.asarray(d["size"]).reshape(-1))
+        c = d["camera"]
+        if "K" not in c:
+            raise ValueError("align target file: missing key camera K")
+        camera = CameraModel(size, c["K"], str(c.get("model", "brown")), c.get("dist", ()))
+        return cls(camera, d["R"], d["T"], rectified=bool(np.asarray(d.get("rectified", False))))
+
+    @classmethod
+    def load(cls, path):
+        """A ``.json`` or ``.npz`` file written by ``save`` (keys size, camera {K, model, dist}, R, T[, rectified]; in an
+        ``.npz`` the camera's as camera_K, camera_model, camera_dist)."""
+        path = os.fspath(path)
+        ext = os.path.splitext(path)[1].lower()
+        if ext == ".json":
+            with open(path) as f:
+                return cls.from_dict(json.load(f))
+        if ext == ".npz":
+            with np.load(path) as z:
+                d = {k: z[k] for k in z.files if not k.startswith("camera_")}
+                if "camera_K" in z.files:
+                    d["camera"] = dict(K=z["camera_K"], model=str(z["camera_model"]) if "camera_model" in z.files else "brown",
+                                       dist=z["camera_dist"] if "camera_dist" in z.files else ())
+            return cls.from_dict(d)
+        raise ValueError(f"align target file: .json or .npz expected, got {path!r}")
+
+    @classmethod
+    def resolve(cls, align_to, rect=None):
+        """What ``LiveSession(align_to=)`` accepts -> an ``AlignTarget``: one is taken as it is, a path is loaded, and
+        "left" / "right" name the rig's own cameras, which only a session with ``calibration=`` (``rect``) has."""
+        if isinstance(align_to, cls):
+            return align_to
+        if align_to in ("left", "right"):
+            if rect is None:
+                raise ValueError(f"align_to={align_to!r} names a camera of the rig: it needs calibration=")
+            return cls.of_rig(rect, align_to)
+        if isinstance(align_to, (str, os.PathLike)):
+            return cls.load(align_to)
+        raise ValueError(f"align_to: an AlignTarget, 'left', 'right' or a path to a .json / .npz file expected, got "
+                         f"{type(align_to).__name__}")
+
+    def __eq__(self, other):
+        return isinstance(other, AlignTarget) and self.camera == other.camera and self.rectified == other.rectified and \
+            np.array_equal(self.R, other.R) and np.array_equal(self.T, other.T)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"AlignTarget({self.camera!r}, R={self.R.tolist()}, T={self.T.tolist()}, rectified={self.rectified})"
 
 
 # ---- files: plain keys, .json or .npz --------------------------------------------------------------------

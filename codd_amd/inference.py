@@ -54,6 +54,14 @@ def parse_args(argv=None):
                    "residual [1, frames, h, w] fp32 (grey levels; NaN where the flags are 1 or 128)")
     p.add_argument("--occ-px", type=float, default=None, help="--confidence: occlusion tolerance in pixels (default 1.0)")
     p.add_argument("--tau", type=float, default=None, help="--confidence: mismatch threshold in grey levels (default 24.0)")
+    p.add_argument("--align", default=None, metavar="left|right|FILE",
+                   help="--live: also write <name>.aligned.pred.npz, key depth, [1, frames, ht, wt] fp32: the depth map "
+                   "(unit of calib) registered to another calibrated camera, +inf where nothing lands: `left` / `right`, the "
+                   "rig's own physical cameras (need --calibration), or a .json / .npz file of a "
+                   "codd_amd.calibration.AlignTarget, see INTEGRATION.md (without --calibration the session's pseudo "
+                   "intrinsics have two focal lengths, which the session rejects)")
+    p.add_argument("--align-footprint", type=int, default=None, choices=[1, 2, 3, 4],
+                   help="--align: target pixels per source pixel and axis (default: the smallest that leaves no hole lines)")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
     p.add_argument("--calibration", help="--live: .json / .npz stereo calibration (or rectification) of the rig, see "
                    "INTEGRATION.md; the frames are rectified from it on the GPU, and intrinsics and calib are those of the "
@@ -99,6 +107,13 @@ def parse_args(argv=None):
         p.error("--confidence needs --live")
     if (args.occ_px is not None or args.tau is not None) and not args.confidence:
         p.error("--occ-px / --tau need --confidence")
+    if args.align is not None:
+        if not args.live:
+            p.error("--align needs --live")
+        if args.align in ("left", "right") and args.calibration is None:
+            p.error(f"--align {args.align} names a camera of the rig: it needs --calibration")
+    elif args.align_footprint is not None:
+        p.error("--align-footprint needs --align")
     return args
 
 
@@ -251,7 +266,8 @@ def run_live(args, model, videos):
     results go to <show-dir>/<name>.disp.pred.npz ([1, frames, h, w], as the default path writes) and, with --motion,
     <name>.motion.pred.npz ([1, frames, h, w, C]; a frame without a field is all NaN) and, with --ego,
     <name>.ego.pred.npz (pose, stats, camera_to_world, moving; a frame without a field is NaN, 255 in moving) and, with
-    --confidence, <name>.conf.pred.npz (flags and residual, [1, frames, h, w] each).  With --pixel-format the frame files
+    --confidence, <name>.conf.pred.npz (flags and residual, [1, frames, h, w] each) and, with --align,
+    <name>.aligned.pred.npz (depth, [1, frames, ht, wt] on the target camera's grid).  With --pixel-format the frame files
     are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU.  With
     --calibration the frames (files or --frame-size) have the calibration's source size and every result has --net-size."""
     from PIL import Image
@@ -263,6 +279,11 @@ def run_live(args, model, videos):
     extra = dict(egomotion=True) if args.ego else {}
     if args.confidence:
         extra["confidence"] = {k: v for k, v in (("occ_px", args.occ_px), ("tau", args.tau)) if v is not None} or True
+    align_to = getattr(args, "align", None)
+    if align_to:
+        extra["align_to"] = align_to
+        if args.align_footprint is not None:
+            extra["align"] = dict(footprint=args.align_footprint)
     raw = getattr(args, "pixel_format", None)
     if raw:
         extra.update(pixel_format=raw, pitch=args.pitch, yuv=args.yuv or "bt601")
@@ -282,7 +303,7 @@ def run_live(args, model, videos):
         if cal and s.src_shape != tuple(src):
             raise ValueError(f"{name}: frames of {src[0]}x{src[1]}, the calibration is for {s.src_shape[0]}x{s.src_shape[1]}")
         s.reset()
-        out = mot = ego = cflags = cres = None
+        out = mot = ego = cflags = cres = aligned = None
         nf = len(lefts)
         pose, stats, world = (np.full((1, nf) + t, np.nan, dt) for t, dt in (((7,), np.float32), ((4,), np.float32),
                                                                              ((4, 4), np.float64)))
@@ -299,11 +320,18 @@ def run_live(args, model, videos):
             if args.confidence:
                 cflags = _NpzStream(osp.join(args.show_dir, name + ".conf.pred.npz"), "flags", (1, nf, h, w), np.uint8)
                 cres = cflags.spool("residual", (1, nf, h, w), np.float32)
+            if align_to:
+                aligned = _NpzStream(osp.join(args.show_dir, name + ".aligned.pred.npz"), "depth",
+                                     (1, nf) + s.align_target.camera.size, np.float32)
         n = 0
         try:
             frames = iter_raw_frames(lefts, rights, raw, src, args.pitch) if raw else iter_frames(lefts, rights)
             for res in live_results(s, frames):
                 n += 1
+                if align_to:
+                    res, al = res[:-1] if (args.motion or args.ego or args.confidence) else res[0], res[-1]
+                    if aligned is not None:
+                        aligned.write(al.depth)
                 if args.confidence:
                     res, c = res[:-1] if (args.motion or args.ego) else res[0], res[-1]
                     if cflags is not None:
@@ -326,7 +354,7 @@ def run_live(args, model, videos):
             if cflags is not None:
                 cflags.abort()
             raise
-        for stream in (out, mot):
+        for stream in (out, mot, aligned):
             if stream is not None:
                 stream.close()
         if ego is not None:

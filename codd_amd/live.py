@@ -35,6 +35,11 @@ With ``calibration=`` the session rectifies from the rig's calibration (codd_amd
 of the rectified image the network sees, frames arrive at the calibration's own source size in either family of formats,
 and ``codd_ingest_calibrated`` stands where the two entries above stand -- it evaluates the rectifying map in registers
 (no map arrays) -- while ``intrinsics`` and ``calib`` of the rectified virtual camera come from the rectification.
+
+With ``align_to=`` the session also hands out the depth map on the grid of another calibrated camera -- a physical camera
+of the rig or a separate colour camera (``calibration.AlignTarget``): ``codd_align_depth`` runs right after
+``codd_export_depth`` on the frame's disparity, forward-warps it into the target camera with a z-buffer (the nearest
+surface wins) and, on request, returns where every pixel of the session's own grid lands in the target image.
 """
 from collections import deque, namedtuple
 
@@ -52,6 +57,7 @@ DEPTH = 2  # frames in flight: input, device and host output slots are double-bu
 DEFAULT_INTRINSICS, DEFAULT_CALIB = (1050.0, 1050.0, 480.0, 270.0), 210.0  # without calibration= and not passed
 EGO_DEFAULTS = dict(iters=5, delta_px=1.0, tau_px=2.0, min_valid=16)
 CONF_DEFAULTS = dict(occ_px=1.0, tau=24.0)
+ALIGN_DEFAULTS = dict(footprint=None, uv=False)  # footprint None: calibration.auto_footprint
 
 # One frame's ego-motion, caller-owned: pose fp32 [7] = (t, q_xyzw) of G, the rigid motion that maps static points from
 # the previous camera frame to the current one (t in the unit of calib; the camera itself moved by G^-1); ok (False: the
@@ -67,6 +73,13 @@ Ego = namedtuple("Ego", "pose ok valid inliers rms_px moving residual camera_to_
 # difference of the left pixel and its match in the right image in grey levels of the 8-bit source, NaN where the flags
 # are 1 or 128.
 Confidence = namedtuple("Confidence", "flags residual")
+
+
+# One frame's depth on the grid of the align_to camera, caller-owned: depth fp32 [ht,wt] in the unit of calib, the nearest
+# surface that lands on each target pixel, +inf where nothing lands; uv fp32 [h,w,2] (None unless align=dict(uv=True)): the
+# position (sx, sy) in the target image of every pixel of the session's own grid, NaN where the pixel has no valid
+# disparity or does not project into the target camera.
+Aligned = namedtuple("Aligned", "depth uv")
 
 
 def pose_matrix(pose):
@@ -138,6 +151,26 @@ def _check_conf(confidence):
         raise ValueError(f"confidence: occ_px >= 0 expected, got {confidence['occ_px']!r}")
     if p["tau"] != p["tau"]:
         raise ValueError("confidence: tau must not be NaN")
+    return p
+
+
+def _check_align(align, align_to):
+    """None -> the defaults; a dict overrides them.  ValueError otherwise, and for ``align`` without ``align_to``."""
+    if align is None:
+        return dict(ALIGN_DEFAULTS)
+    if align_to is None:
+        raise ValueError("align: needs align_to=")
+    if not isinstance(align, dict):
+        raise ValueError(f"align: None or a dict of {tuple(ALIGN_DEFAULTS)} expected, got {align!r}")
+    unknown = set(align) - set(ALIGN_DEFAULTS)
+    if unknown:
+        raise ValueError(f"align: unknown keys {sorted(unknown)}; known: {tuple(ALIGN_DEFAULTS)}")
+    p = dict(ALIGN_DEFAULTS, **align)
+    k = p["footprint"]
+    if k is not None and not (isinstance(k, int) and not isinstance(k, bool) and 1 <= k <= ops.ALIGN_MAX_FOOTPRINT):
+        raise ValueError(f"align: footprint None or an integer in [1, {ops.ALIGN_MAX_FOOTPRINT}] expected, got {k!r}")
+    if not isinstance(p["uv"], bool):
+        raise ValueError(f"align: uv True or False expected, got {p['uv']!r}")
     return p
 
 
@@ -251,7 +284,7 @@ class LiveSession:
 
     ``egomotion`` (False, True, or a dict overriding ``iters``, ``delta_px``, ``tau_px``, ``min_valid``): ``pop`` and
     ``step`` also return an ``Ego`` (or None for a frame without a field).  The tuple order is fixed:
-    ``result[, motion][, ego][, confidence]``, each part present iff requested.
+    ``result[, motion][, ego][, confidence][, aligned]``, each part present iff requested.
 
     ``confidence`` (False, True, or a dict overriding ``occ_px`` (1.0 pixel) and ``tau`` (24.0 grey levels)): ``pop`` and
     ``step`` also return a ``Confidence(flags, residual)`` on the CURRENT frame's grid, for every frame (never None).  It
@@ -269,11 +302,23 @@ class LiveSession:
     what every result has), frames have the calibration's source size (``src_shape``; ``pitch`` and the format's size
     rules apply to it), and ``intrinsics`` and ``calib`` are those of the rectified virtual camera -- passing either, or
     ``rectify=``, next to ``calibration`` is a ValueError.  The map is defined in include/codd_hip.h (THE MAP FUNCTION).
+
+    ``align_to`` (a ``calibration.AlignTarget``, a path to a ``.json`` / ``.npz`` file of one, or "left" / "right", the
+    rig's own physical cameras, which need ``calibration=``): ``pop`` and ``step`` also return an ``Aligned(depth, uv)``,
+    for every frame (never None), last in the tuple: ``depth`` fp32 [ht,wt] on the target camera's grid (its
+    ``camera.size``) in the unit of ``calib``, the nearest surface per pixel and +inf where nothing lands, whatever
+    ``output`` is.  The target's pose ``X_target = R X_left + T`` starts from the physical left camera when the session
+    has ``calibration=`` and from the session's own (rectified) camera otherwise, which must then have one focal length
+    (``intrinsics[0] == intrinsics[1]``).  ``align`` (None or a dict overriding ``ALIGN_DEFAULTS``): ``footprint`` (1 .. 4;
+    None: ``calibration.auto_footprint``, the smallest that leaves no hole lines) is the side of the square of target
+    pixels each source pixel covers -- 1 leaves lines of holes where the target magnifies, more widens foreground
+    edges; ``uv`` True also returns ``uv`` fp32 [h,w,2], where each pixel of the session's grid lands in the target image
+    (NaN: nowhere).  ``align`` without ``align_to`` is a ValueError.  Defined in include/codd_hip.h (codd_align_depth).
     """
 
     def __init__(self, estimator, shape, intrinsics=None, calib=None, output="depth",
                  bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False,
-                 pixel_format="rgb8", yuv="bt601", pitch=None, calibration=None, zoom=1.0):
+                 pixel_format="rgb8", yuv="bt601", pitch=None, calibration=None, zoom=1.0, align_to=None, align=None):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
@@ -301,6 +346,19 @@ class LiveSession:
             raise ValueError("zoom: needs calibration=")
         intrinsics = DEFAULT_INTRINSICS if intrinsics is None else intrinsics
         calib = DEFAULT_CALIB if calib is None else calib
+        self.align = _check_align(align, align_to)
+        self.align_target = None
+        if align_to is not None:
+            self.align_target = _calibration.AlignTarget.resolve(align_to, self.rect)
+            if float(intrinsics[0]) != float(intrinsics[1]):
+                raise ValueError(f"align_to: the session's camera must have one focal length (fx == fy), got intrinsics "
+                                 f"{tuple(intrinsics)}")
+            self._align_K = tuple(float(v) for v in intrinsics)
+            self._align_view = ops.align_view(self.align_target, self.rect)  # (a ctypes struct: no device call)
+            if self.align["footprint"] is None:
+                R = np.array(self._align_view.R[:], np.float64).reshape(3, 3)
+                self.align["footprint"] = _calibration.auto_footprint(R, self.align_target.camera, (h, w), self._align_K,
+                                                                      r2_max=self._align_view.r2_max)
         self.src_shape = (h, w) if self.rect is None else self.rect.size  # the size of a frame as the camera hands it out
         # (rows, row_bytes, pitch, nbytes) of a source frame; ValueError if invalid
         self._layout = frame_layout(pixel_format, self.src_shape[0], self.src_shape[1], pitch)
@@ -368,6 +426,11 @@ class LiveSession:
                                 torch.empty(h, w, dtype=torch.float32, device=dev))
                 self._h_conf = [(torch.empty(h, w, dtype=torch.uint8, pin_memory=True),
                                  torch.empty(h, w, dtype=torch.float32, pin_memory=True)) for _ in range(DEPTH)]
+            if self.align_target is not None:
+                shapes = (self.align_target.camera.size,) + (((h, w, 2),) if self.align["uv"] else ())
+                self._d_align = tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in shapes)
+                self._h_align = [tuple(torch.empty(s, dtype=torch.float32, pin_memory=True) for s in shapes)
+                                 for _ in range(DEPTH)]
             self._s_up, self._s_down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             ev = lambda: [torch.cuda.Event() for _ in range(DEPTH)]  # noqa: E731
             self._e_up, self._e_ingest, self._e_export, self._e_down = ev(), ev(), ev(), ev()
@@ -426,6 +489,9 @@ class LiveSession:
             if self._pushed > 0:
                 compute.wait_event(self._e_down[(self._pushed - 1) % DEPTH])  # one device staging buffer
             ops.export_depth(disp, self._d_out, mode=self.output, calib=self.calib)
+            if self.align_target is not None:
+                ops.align_depth(disp, self.shape, self._align_K, self.calib, self._align_view, self.align_target.camera.size,
+                                self.align["footprint"], self._d_align[0], self._d_align[1] if self.align["uv"] else None)
             if self.conf is not None:
                 # step_fill calls fill exactly once per frame, on every path: the buffers it was handed are this frame's
                 assert len(images) == 2, "FrameRunner.step_fill did not call fill(left, right)"
@@ -457,6 +523,9 @@ class LiveSession:
                 if self.conf is not None:
                     for host, dev_buf in zip(self._h_conf[k], self._d_conf):
                         host.copy_(dev_buf, non_blocking=True)
+                if self.align_target is not None:
+                    for host, dev_buf in zip(self._h_align[k], self._d_align):
+                        host.copy_(dev_buf, non_blocking=True)
                 self._e_down[k].record(self._s_down)
         self._inflight.append(k)
         self._pushed += 1
@@ -473,6 +542,9 @@ class LiveSession:
             out.append(self._collect_ego(k))
         if self.conf is not None:
             out.append(Confidence(*(t.numpy().copy() for t in self._h_conf[k])))
+        if self.align_target is not None:
+            got = [t.numpy().copy() for t in self._h_align[k]]
+            out.append(Aligned(got[0], got[1] if self.align["uv"] else None))
         return out[0] if len(out) == 1 else tuple(out)
 
     def _collect_ego(self, k):
@@ -487,7 +559,7 @@ class LiveSession:
     def pop(self):
         """The oldest frame's result: numpy [h,w] (fp32, or uint16 for ``disp_u16``), owned by the caller; with a
         ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None; with ``egomotion``, an ``Ego`` or None
-        follows; with ``confidence``, a ``Confidence`` comes last."""
+        follows; with ``confidence``, a ``Confidence``; with ``align_to``, an ``Aligned`` comes last."""
         if self._ready:
             return self._ready.popleft()
         if not self._inflight:
@@ -517,7 +589,7 @@ class LiveSession:
             torch.cuda.current_stream(self.dev).synchronize()
             self._s_down.synchronize()
             for name in ("_h_in", "_d_in", "_scratch", "_maps", "_d_out", "_h_out", "_depth_prev", "_d_mot", "_h_mot",
-                         "_d_ego", "_h_ego", "_ego_scratch", "_d_conf", "_h_conf"):
+                         "_d_ego", "_h_ego", "_ego_scratch", "_d_conf", "_h_conf", "_d_align", "_h_align"):
                 setattr(self, name, None)
             self._open_done = False
         self._inflight.clear()

@@ -2041,6 +2041,51 @@ def export_confidence(disp, flags, residual=None, left=None, right=None, crop=No
     return flags
 
 
+ALIGN_MAX_FOOTPRINT = 4  # CODD_ALIGN_MAX_FOOTPRINT of include/codd_hip.h
+
+
+def align_view(target, rect=None):
+    """The ``codd_align_view`` struct of a ``calibration.AlignTarget``: its pose taken from the rectified left camera of
+    ``rect`` (a ``calibration.Rectification``; None: the target's pose already refers to the grid of the disparity), its
+    camera, and ``r2_max`` = ``calibration.fold_radius2`` of that camera.  No device call."""
+    from . import calibration
+    R, T = target.pose_from(rect)
+    s = _abi.AlignView()
+    s.R[:] = [float(x) for row in R for x in row]
+    s.T[:] = [float(x) for x in T]
+    s.K[:] = target.camera.K
+    s.dist[:] = target.camera.dist8
+    s.r2_max = calibration.fold_radius2(target.camera)
+    s.model = CALIB_MODELS[target.camera.model]
+    return s
+
+
+def align_depth(disp, shape, intrinsics, calib, view, target_size, footprint, depth_out, uv_out=None):
+    """A fill and one launch per frame: the padded disparity ``disp`` [H,W] (or [1,1,H,W]) of the rectified left camera with
+    ``intrinsics`` (f', f', cx', cy') and ``calib`` = f' * baseline, read inside ``shape`` = (h, w), forward-warped into the
+    camera ``view`` (``align_view``) of ``target_size`` = (ht, wt): ``depth_out`` fp32 [ht,wt] (caller-owned) gets the depth
+    of the nearest surface that lands on each target pixel, in the unit of ``calib``, +inf where nothing lands; each
+    source pixel covers the ``footprint`` x ``footprint`` (1 .. 4) target pixels nearest to its position.  ``uv_out`` fp32
+    [h,w,2] or None gets that position (sx, sy), NaN where the pixel has no valid disparity or does not project
+    (include/codd_hip.h, codd_align_depth)."""
+    lib = _abi.load()
+    _require_gpu(disp)
+    H, W = disp.shape[-2:]
+    h, w = int(shape[0]), int(shape[1])
+    ht, wt = int(target_size[0]), int(target_size[1])
+    f, fy, cx, cy = (float(v) for v in intrinsics)
+    if f != fy:
+        raise ValueError(f"intrinsics: the rectified camera has one focal length (f', f', cx', cy'), got {tuple(intrinsics)}")
+    assert disp.dtype == torch.float32 and disp.is_cuda and disp.is_contiguous() and disp.numel() == H * W
+    assert depth_out.dtype == torch.float32 and depth_out.is_cuda and depth_out.is_contiguous() and tuple(depth_out.shape) == (ht, wt)
+    if uv_out is not None:
+        assert uv_out.dtype == torch.float32 and uv_out.is_cuda and uv_out.is_contiguous() and tuple(uv_out.shape) == (h, w, 2)
+    _abi.check(lib.codd_align_depth(disp.data_ptr(), H, W, h, w, f, cx, cy, float(calib), C.byref(view), ht, wt,
+                                    int(footprint), depth_out.data_ptr(), None if uv_out is None else uv_out.data_ptr(),
+                                    _stream()), "align_depth")
+    return depth_out
+
+
 def fusion_select(mode, cur, warp, gt=None, K=0.5):
     """mode 'kalman' / 'gt' (ablation fusions).  cur, warp [B,1,H,W]; gt [B,1,hg,wg]."""
     lib = _abi.load()

@@ -808,6 +808,52 @@ int codd_export_confidence(const float* disp, const float* left, const float* ri
                            const float* stdv, float occ_px, float tau, unsigned char* flags, float* residual,
                            void* stream);
 
+/* Live-session depth on another camera's grid (codd_amd/live.py, align_to=): the frame's disparity, which lives on the
+ * rectified virtual left camera, forward-warped into a calibrated target camera -- a physical camera of the rig or a
+ * separate colour camera -- with occlusions resolved to the nearest surface.  The reference has no such output; this
+ * replaces the z-buffered forward warp a user writes on the host.  Two launches (a fill and the splat), no allocation,
+ * no host synchronisation.
+ * disp [H,W]: the frame's padded disparity, read inside [0,h) x [0,w) only; f, cx, cy: the rectified camera (f' = fx' =
+ * fy'); calib = f' * baseline.  depth_out fp32 [ht,wt] and uv_out fp32 [h,w,2] (may be NULL) are caller-owned and
+ * contiguous; neither needs more than float alignment.
+ * The target is a codd_align_view, all doubles except model: R (row-major) and T, X_t = R X_rect + T with T in the unit
+ * of calib / f'; K = (fx, fy, cx, cy), dist and model, the target camera, with the meaning they have in codd_calib_view;
+ * r2_max: a point whose normalised radius^2 in the target exceeds it is not projected (a Brown polynomial folds back
+ * outside its field of view and would land far-off points inside the image).  The entry rounds R, T, K, dist and r2_max
+ * ONCE to fp32.
+ * Per source pixel (u, v), in this fp32 operation order (fma = one fused multiply-add, every other operation rounded to
+ * nearest on its own; u, v the pixel's integer coordinates as floats; division and sqrt correctly rounded):
+ *   d = disp[v,u];  !(0 < d < +inf)  ->  skipped                                            (false for NaN)
+ *   Z = (1 / d) * calib                                         (the bits codd_export_depth's CODD_EXPORT_DEPTH gives)
+ *   X = ((u - cx) / f) * Z;  Y = ((v - cy) / f) * Z
+ *   Xt = fma(R0, X, fma(R1, Y, fma(R2, Z, T0)));  Yt = fma(R3, X, fma(R4, Y, fma(R5, Z, T1)))
+ *   Zt = fma(R6, X, fma(R7, Y, fma(R8, Z, T2)));  !(0 < Zt < +inf)  ->  skipped
+ *   x = Xt / Zt;  y = Yt / Zt;  r2 = fma(y, y, x * x);  !(r2 <= r2_max)  ->  skipped
+ *   (sx, sy): THE MAP FUNCTION above from its line `xx = x * x` on (the target's lens and K);  sx or sy not finite -> skipped
+ * uv_out[v,u] = (sx, sy), or NaN in both for a skipped pixel -- written whether or not the position lies inside the target.
+ * footprint k in 1 .. CODD_ALIGN_MAX_FOOTPRINT: a pixel that was not skipped offers Zt to the k target columns nearest
+ * to sx, odd k: rint(sx) - (k-1)/2 .. rint(sx) + (k-1)/2 (rint: ties to even), even k: floor(sx) - (k/2 - 1) .. floor(sx) +
+ * k/2, and likewise to the k rows nearest to sy; those inside [0,ht) x [0,wt) take min(current, Zt).  A target pixel that
+ * nothing reached holds +inf (what CODD_EXPORT_DEPTH gives for zero disparity).  k = 1 leaves lines of holes where the map
+ * magnifies; k > 1 closes them and widens every foreground edge by up to k - 1 pixels.
+ * Equal inputs give equal bytes: the minimum is a 32-bit integer atomic minimum over the bits of Zt (positive floats
+ * order like their bit patterns, +inf above them all), which does not depend on arrival order.
+ * CODD_EINVAL, before any launch: disp, view or depth_out NULL; a non-positive size, h > H or w > W; h w or ht wt >= 2^31;
+ * f or calib not positive and finite, cx or cy not finite; an unknown model; a non-finite entry in the struct; fx, fy or
+ * r2_max not > 0 (as doubles or once rounded to fp32); footprint outside 1 .. CODD_ALIGN_MAX_FOOTPRINT. */
+#define CODD_ALIGN_MAX_FOOTPRINT 4
+typedef struct codd_align_view {
+  double R[9];
+  double T[3];
+  double K[4];
+  double dist[8];
+  double r2_max;
+  int model;
+} codd_align_view;
+int codd_align_depth(const float* disp, int H, int W, int h, int w, float f, float cx, float cy, float calib,
+                     const codd_align_view* view, int ht, int wt, int footprint, float* depth_out, float* uv_out,
+                     void* stream);
+
 /* Ablation plug-ins.  codd_fusion_select: mode 0 = KalmanFusion (model/fusion/others.py:124-153; constant
  * gain K = Q/(Q+R), the reference never updates P), mode 1 = GTFusion (:54-86; gt [B,1,hg,wg], zero-padded).
  * cur, warp, out: [B,1,H,W]. */
