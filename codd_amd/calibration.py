@@ -241,6 +241,26 @@ class Rectification:
         vv, uu = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
         return self.source_points(view, uu, vv)
 
+    # ---- the correction a live session's rectification check found (live.Epipolar, live.combine_epipolar) ---------
+    def corrected(self, coef):
+        """A new ``Rectification`` that takes out the vertical disparity ``dy = f' (c0 (1 + yn^2) + c1 xr yn + c2 xr + c3 yn)``
+        which a session rectified with THIS one measured (``coef`` = (c0, c1, c2, c3): ``live.Epipolar.coef`` or
+        ``live.combine_epipolar``).  That map says that the right rectified view shows every ray rotated by ``R_w =
+        rodrigues((-c0, c1, c2))`` and magnified by ``1 + c3``; so the right view's rectifying rotation becomes ``R_w^T R2``
+        (the inverse of the fitted rotation on its ``R``) and the right ``CameraModel``'s ``fx`` and ``fy`` are multiplied
+        by ``1 + c3`` (the focal length the lens really has, which divides the magnification out of the map).  The left
+        view, ``P``, ``shape`` and ``baseline`` are untouched.  First order: what is left is of the order ``|coef|`` times
+        what was there; check again with the corrected rectification and apply ``corrected`` to the result if need be."""
+        c = _finite(coef, "coef", (4,))
+        if not 1.0 + c[3] > 0:
+            raise ValueError(f"coef: a focal ratio 1 + c3 > 0 is expected, got c3 = {c[3]}")
+        left, right = self.views
+        fx, fy, cx, cy = right.camera.K
+        camera = CameraModel(right.camera.size, (fx * (1.0 + c[3]), fy * (1.0 + c[3]), cx, cy), right.camera.model,
+                             right.camera.dist)
+        R = rodrigues([-c[0], c[1], c[2]]).T @ np.asarray(right.R, np.float64)
+        return Rectification(left, RectifiedView(R, right.P, camera), self.shape, self.baseline)
+
     # ---- files -----------------------------------------------------------------------------------------
     def to_dict(self):
         return dict(size=list(self.size), left=self.views[0].camera.to_dict(), right=self.views[1].camera.to_dict(),

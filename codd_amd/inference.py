@@ -60,6 +60,11 @@ def parse_args(argv=None):
                    "rig's own physical cameras (need --calibration), or a .json / .npz file of a "
                    "codd_amd.calibration.AlignTarget, see INTEGRATION.md (without --calibration the session's pseudo "
                    "intrinsics have two focal lengths, which the session rejects)")
+    p.add_argument("--epipolar", action="store_true",
+                   help="--live: rectification health check; also write <name>.epi.pred.npz: coef [1, frames, 4] (the fitted "
+                        "vertical disparity: a rotation of the right view by (-c0, c1, c2) rad and a focal error c3), stats "
+                        "[1, frames, 5] (ok, measurable, inliers, rms_px, rms_fit_px), A [1, frames, 4, 4] and b [1, frames, 4] "
+                        "(each frame's normal equations), combined [4] and combined_ok (live.combine_epipolar over the video)")
     p.add_argument("--align-footprint", type=int, default=None, choices=[1, 2, 3, 4],
                    help="--align: target pixels per source pixel and axis (default: the smallest that leaves no hole lines)")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
@@ -107,6 +112,8 @@ def parse_args(argv=None):
         p.error("--confidence needs --live")
     if (args.occ_px is not None or args.tau is not None) and not args.confidence:
         p.error("--occ-px / --tau need --confidence")
+    if args.epipolar and not args.live:
+        p.error("--epipolar needs --live")
     if args.align is not None:
         if not args.live:
             p.error("--align needs --live")
@@ -267,11 +274,13 @@ def run_live(args, model, videos):
     <name>.motion.pred.npz ([1, frames, h, w, C]; a frame without a field is all NaN) and, with --ego,
     <name>.ego.pred.npz (pose, stats, camera_to_world, moving; a frame without a field is NaN, 255 in moving) and, with
     --confidence, <name>.conf.pred.npz (flags and residual, [1, frames, h, w] each) and, with --align,
-    <name>.aligned.pred.npz (depth, [1, frames, ht, wt] on the target camera's grid).  With --pixel-format the frame files
-    are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU.  With
+    <name>.aligned.pred.npz (depth, [1, frames, ht, wt] on the target camera's grid) and, with --epipolar,
+    <name>.epi.pred.npz (per-frame coefficients, counts, rms and normal equations plus the combined coefficients; one line
+    with the rms vertical disparity and the combined rotation is printed with or without --show).  With --pixel-format the
+    frame files are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU.  With
     --calibration the frames (files or --frame-size) have the calibration's source size and every result has --net-size."""
     from PIL import Image
-    from .live import LiveSession
+    from .live import LiveSession, combine_epipolar
     maps = None
     if args.rectify_maps:
         z = np.load(args.rectify_maps)
@@ -284,6 +293,8 @@ def run_live(args, model, videos):
         extra["align_to"] = align_to
         if args.align_footprint is not None:
             extra["align"] = dict(footprint=args.align_footprint)
+    if getattr(args, "epipolar", False):
+        extra["epipolar"] = True
     raw = getattr(args, "pixel_format", None)
     if raw:
         extra.update(pixel_format=raw, pitch=args.pitch, yuv=args.yuv or "bt601")
@@ -323,11 +334,14 @@ def run_live(args, model, videos):
             if align_to:
                 aligned = _NpzStream(osp.join(args.show_dir, name + ".aligned.pred.npz"), "depth",
                                      (1, nf) + s.align_target.camera.size, np.float32)
-        n = 0
+        n, epis = 0, []
         try:
             frames = iter_raw_frames(lefts, rights, raw, src, args.pitch) if raw else iter_frames(lefts, rights)
             for res in live_results(s, frames):
                 n += 1
+                if "epipolar" in extra:
+                    res, ep = res[:-1] if (args.motion or args.ego or args.confidence or align_to) else res[0], res[-1]
+                    epis.append(ep)
                 if align_to:
                     res, al = res[:-1] if (args.motion or args.ego or args.confidence) else res[0], res[-1]
                     if aligned is not None:
@@ -361,6 +375,19 @@ def run_live(args, model, videos):
             ego.close(dict(pose=pose, stats=stats, camera_to_world=world))
         if cflags is not None:
             cflags.close()
+        if "epipolar" in extra:
+            coef, ok = combine_epipolar(epis)
+            if args.show:
+                np.savez(osp.join(args.show_dir, name + ".epi.pred.npz"), coef=np.array([[e.coef for e in epis]]),
+                         stats=np.array([[(e.ok, e.valid, e.inliers, e.rms_px, e.rms_fit_px) for e in epis]], np.float64),
+                         A=np.array([[e.A for e in epis]]), b=np.array([[e.b for e in epis]]), combined=coef,
+                         combined_ok=np.array(ok))
+            nv = sum(e.valid for e in epis)
+            mean = float(np.sqrt(sum(e.valid * e.rms_px ** 2 for e in epis) / nv)) if nv else 0.0
+            mdeg = np.degrees([-coef[0], coef[1], coef[2]]) * 1e3
+            print(f"{name}: epipolar: rms vertical disparity {mean:.3f} px over {nv} pixels; combined rotation of the right "
+                  f"view ({mdeg[0]:+.1f}, {mdeg[1]:+.1f}, {mdeg[2]:+.1f}) millidegrees, focal ratio {1 + coef[3]:.5f}"
+                  f"{'' if ok else ' (not determined: too little texture)'}")
         print(f"{name}: {n} frames")
     for s in sessions.values():
         s.close()

@@ -40,6 +40,12 @@ With ``align_to=`` the session also hands out the depth map on the grid of anoth
 of the rig or a separate colour camera (``calibration.AlignTarget``): ``codd_align_depth`` runs right after
 ``codd_export_depth`` on the frame's disparity, forward-warps it into the target camera with a z-buffer (the nearest
 surface wins) and, on request, returns where every pixel of the session's own grid lands in the target image.
+
+With ``epipolar=`` the session checks the assumption all of the above rests on, that the calibration still describes the
+rig: ``codd_epipolar_check`` runs right after ``codd_export_confidence`` on the same disparity and normalised images,
+measures per pixel the row offset at which the right image really matches, and fits a small rotation of the right view
+plus a focal ratio to that map; ``combine_epipolar`` pools the frames' normal equations and ``calibration.Rectification
+.corrected`` applies the result.  It needs no motion stage and no ``calibration=``.
 """
 from collections import deque, namedtuple
 
@@ -58,6 +64,7 @@ DEFAULT_INTRINSICS, DEFAULT_CALIB = (1050.0, 1050.0, 480.0, 270.0), 210.0  # wit
 EGO_DEFAULTS = dict(iters=5, delta_px=1.0, tau_px=2.0, min_valid=16)
 CONF_DEFAULTS = dict(occ_px=1.0, tau=24.0)
 ALIGN_DEFAULTS = dict(footprint=None, uv=False)  # footprint None: calibration.auto_footprint
+EPI_DEFAULTS = dict(range_px=2, step=2, tau=24.0, min_curv=0.5, iters=4, delta_px=0.25, min_valid=256, map=False)
 
 # One frame's ego-motion, caller-owned: pose fp32 [7] = (t, q_xyzw) of G, the rigid motion that maps static points from
 # the previous camera frame to the current one (t in the unit of calib; the camera itself moved by G^-1); ok (False: the
@@ -80,6 +87,63 @@ Confidence = namedtuple("Confidence", "flags residual")
 # position (sx, sy) in the target image of every pixel of the session's own grid, NaN where the pixel has no valid
 # disparity or does not project into the target camera.
 Aligned = namedtuple("Aligned", "depth uv")
+
+
+# One frame's rectification check, caller-owned: coef float64 [4] = (c0, c1, c2, c3) of the fitted vertical disparity
+# dy = fy (c0 (1 + yn^2) + c1 xr yn + c2 xr + c3 yn) -- the right view is rotated by (-c0, c1, c2) radians and its focal
+# length is off by the ratio c3; ok (False: the frame alone does not determine the fit and coef is its last good iterate);
+# valid measurable pixels, inliers of the fit; rms_px of the measured dy and rms_fit_px of the inliers' residual;
+# A float64 [4,4] and b float64 [4], the last step's normal equations (combine_epipolar adds them over frames); dy fp32
+# [h,w] (None unless epipolar=dict(map=True)): the measured row offset, L(x, y) ~ R(x - d, y + dy), NaN where not measured.
+Epipolar = namedtuple("Epipolar", "coef ok valid inliers rms_px rms_fit_px A b dy")
+
+
+def epipolar_from_record(rec, dy=None):
+    """The 32 doubles of codd_epipolar_check (include/codd_hip.h) -> ``Epipolar``."""
+    rec = np.asarray(rec, np.float64)
+    A = np.zeros((4, 4))
+    A[np.triu_indices(4)] = rec[10:20]
+    A = A + np.triu(A, 1).T
+    return Epipolar(rec[0:4].copy(), bool(rec[4] != 0), int(rec[5]), int(rec[6]), float(rec[7]), float(rec[8]), A,
+                    rec[20:24].copy(), dy)
+
+
+def solve_epipolar(A, b):
+    """``(coef, ok)`` of the normal equations ``A c = b``: the 4x4 Cholesky and the pivot rule of codd_epipolar_check
+    (a pivot <= 1e-12 trace(A), or anything not finite: zeros and False)."""
+    A, b = np.array(A, np.float64), np.array(b, np.float64)
+    if A.shape != (4, 4) or b.shape != (4,) or not (np.all(np.isfinite(A)) and np.all(np.isfinite(b))):
+        return np.zeros(4), False
+    floor_ = 1e-12 * np.trace(A)
+    L = np.zeros((4, 4))
+    for j in range(4):
+        d = A[j, j] - L[j, :j] @ L[j, :j]
+        if not d > floor_:
+            return np.zeros(4), False
+        L[j, j] = np.sqrt(d)
+        for i in range(j + 1, 4):
+            L[i, j] = (A[i, j] - L[i, :j] @ L[j, :j]) / L[j, j]
+    y = np.zeros(4)
+    for i in range(4):
+        y[i] = (b[i] - L[i, :i] @ y[:i]) / L[i, i]
+    c = np.zeros(4)
+    for i in range(3, -1, -1):
+        c[i] = (y[i] - L[i + 1:, i] @ c[i + 1:]) / L[i, i]
+    if not np.all(np.isfinite(c)):
+        return np.zeros(4), False
+    return c, True
+
+
+def combine_epipolar(results):
+    """``(coef, ok)`` over several frames: the ``Epipolar``s' normal equations ``A``, ``b`` summed in float64 and solved
+    once.  Every frame takes part, those whose own ``ok`` is False too: a single frame often lacks the texture or the
+    spread of disparities that the sequence has.  None entries (and an empty list: ok False) are allowed."""
+    A, b = np.zeros((4, 4)), np.zeros(4)
+    for r in results:
+        if r is not None:
+            A += np.asarray(r.A, np.float64)
+            b += np.asarray(r.b, np.float64)
+    return solve_epipolar(A, b)
 
 
 def pose_matrix(pose):
@@ -151,6 +215,37 @@ def _check_conf(confidence):
         raise ValueError(f"confidence: occ_px >= 0 expected, got {confidence['occ_px']!r}")
     if p["tau"] != p["tau"]:
         raise ValueError("confidence: tau must not be NaN")
+    return p
+
+
+def _check_epi(epipolar):
+    """False / None -> None; True -> the defaults; a dict overrides them.  ValueError otherwise (no device call)."""
+    if epipolar is None or epipolar is False:
+        return None
+    if epipolar is True:
+        return dict(EPI_DEFAULTS)
+    if not isinstance(epipolar, dict):
+        raise ValueError(f"epipolar: False, True or a dict of {tuple(EPI_DEFAULTS)} expected, got {epipolar!r}")
+    unknown = set(epipolar) - set(EPI_DEFAULTS)
+    if unknown:
+        raise ValueError(f"epipolar: unknown keys {sorted(unknown)}; known: {tuple(EPI_DEFAULTS)}")
+    p = dict(EPI_DEFAULTS, **epipolar)
+    for k, lo, hi in (("range_px", 1, 4), ("step", 1, 8), ("iters", 1, 32)):
+        if not (isinstance(p[k], int) and not isinstance(p[k], bool) and lo <= p[k] <= hi):
+            raise ValueError(f"epipolar: an integer {k} in [{lo}, {hi}] expected, got {p[k]!r}")
+    if not (isinstance(p["min_valid"], int) and not isinstance(p["min_valid"], bool)):
+        raise ValueError(f"epipolar: an integer min_valid expected, got {p['min_valid']!r}")
+    for k in ("tau", "min_curv", "delta_px"):
+        try:
+            p[k] = float(p[k])
+        except (TypeError, ValueError):
+            raise ValueError(f"epipolar: a number expected for {k}, got {p[k]!r}") from None
+        if p[k] != p[k]:
+            raise ValueError(f"epipolar: {k} must not be NaN")
+    if not p["delta_px"] > 0:
+        raise ValueError(f"epipolar: positive delta_px expected, got {p['delta_px']!r}")
+    if not isinstance(p["map"], bool):
+        raise ValueError(f"epipolar: map True or False expected, got {p['map']!r}")
     return p
 
 
@@ -284,7 +379,7 @@ class LiveSession:
 
     ``egomotion`` (False, True, or a dict overriding ``iters``, ``delta_px``, ``tau_px``, ``min_valid``): ``pop`` and
     ``step`` also return an ``Ego`` (or None for a frame without a field).  The tuple order is fixed:
-    ``result[, motion][, ego][, confidence][, aligned]``, each part present iff requested.
+    ``result[, motion][, ego][, confidence][, aligned][, epipolar]``, each part present iff requested.
 
     ``confidence`` (False, True, or a dict overriding ``occ_px`` (1.0 pixel) and ``tau`` (24.0 grey levels)): ``pop`` and
     ``step`` also return a ``Confidence(flags, residual)`` on the CURRENT frame's grid, for every frame (never None).  It
@@ -314,11 +409,20 @@ class LiveSession:
     pixels each source pixel covers -- 1 leaves lines of holes where the target magnifies, more widens foreground
     edges; ``uv`` True also returns ``uv`` fp32 [h,w,2], where each pixel of the session's grid lands in the target image
     (NaN: nowhere).  ``align`` without ``align_to`` is a ValueError.  Defined in include/codd_hip.h (codd_align_depth).
+
+    ``epipolar`` (False, True, or a dict overriding ``EPI_DEFAULTS``): ``pop`` and ``step`` also return an ``Epipolar``,
+    for every frame (never None), last in the tuple: the vertical disparity the frame's own images show under the frame's
+    disparity, fitted by a rotation of the right view and a focal ratio.  ``range_px`` (1 .. 4) rows are searched either
+    way at every ``step``-th (1 .. 8) column and row; a pixel counts when its best match costs at most ``tau`` grey levels
+    per pixel and the cost's curvature across rows exceeds ``min_curv``; ``iters`` (1 .. 32) re-weighted steps with the
+    Cauchy scale ``delta_px``; fewer than ``min_valid`` pixels make ``ok`` False; ``map`` True also returns the per-pixel
+    ``dy``.  It needs no motion stage and no ``calibration=``.  Defined in include/codd_hip.h (codd_epipolar_check).
     """
 
     def __init__(self, estimator, shape, intrinsics=None, calib=None, output="depth",
                  bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False,
-                 pixel_format="rgb8", yuv="bt601", pitch=None, calibration=None, zoom=1.0, align_to=None, align=None):
+                 pixel_format="rgb8", yuv="bt601", pitch=None, calibration=None, zoom=1.0, align_to=None, align=None,
+                 epipolar=False):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
@@ -329,6 +433,7 @@ class LiveSession:
         if self.ego is not None and getattr(estimator, "motion", None) is None:
             raise ValueError(f"egomotion={egomotion!r} needs an estimator with a motion stage (this one has none)")
         self.conf = _check_conf(confidence)
+        self.epi = _check_epi(epipolar)
         h, w = int(shape[0]), int(shape[1])
         if h <= 0 or w <= 0:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
@@ -359,6 +464,7 @@ class LiveSession:
                 R = np.array(self._align_view.R[:], np.float64).reshape(3, 3)
                 self.align["footprint"] = _calibration.auto_footprint(R, self.align_target.camera, (h, w), self._align_K,
                                                                       r2_max=self._align_view.r2_max)
+        self._epi_K = tuple(float(v) for v in intrinsics)
         self.src_shape = (h, w) if self.rect is None else self.rect.size  # the size of a frame as the camera hands it out
         # (rows, row_bytes, pitch, nbytes) of a source frame; ValueError if invalid
         self._layout = frame_layout(pixel_format, self.src_shape[0], self.src_shape[1], pitch)
@@ -431,6 +537,12 @@ class LiveSession:
                 self._d_align = tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in shapes)
                 self._h_align = [tuple(torch.empty(s, dtype=torch.float32, pin_memory=True) for s in shapes)
                                  for _ in range(DEPTH)]
+            if self.epi is not None:
+                self._d_epi = (torch.zeros(32, dtype=torch.float64, device=dev),) + (
+                    (torch.empty(h, w, dtype=torch.float32, device=dev),) if self.epi["map"] else ())
+                self._h_epi = [tuple(torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_epi)
+                               for _ in range(DEPTH)]
+                self._epi_scratch = torch.empty(ops.epipolar_scratch(h, w), dtype=torch.uint8, device=dev)
             self._s_up, self._s_down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             ev = lambda: [torch.cuda.Event() for _ in range(DEPTH)]  # noqa: E731
             self._e_up, self._e_ingest, self._e_export, self._e_down = ev(), ev(), ev(), ev()
@@ -473,7 +585,7 @@ class LiveSession:
             images = []  # (emptied per frame: a fill that is skipped cannot leave the previous frame's buffers here)
 
             def fill(left, right):
-                images[:] = (left, right)  # (the frame's normalised images: read again by export_confidence)
+                images[:] = (left, right)  # (the frame's normalised images: export_confidence and epipolar_check read them)
                 if self.rect is not None:
                     ops.ingest_calibrated(self._d_in[k][0], self._d_in[k][1], left, right, self._calib_views,
                                           self.pixel_format, self.src_shape, self.shape, bgr=self.bgr, yuv=self.yuv,
@@ -496,6 +608,11 @@ class LiveSession:
                 # step_fill calls fill exactly once per frame, on every path: the buffers it was handed are this frame's
                 assert len(images) == 2, "FrameRunner.step_fill did not call fill(left, right)"
                 ops.export_confidence(disp, self._d_conf[0], self._d_conf[1], images[0], images[1], **self.conf)
+            if self.epi is not None:
+                assert len(images) == 2, "FrameRunner.step_fill did not call fill(left, right)"
+                ops.epipolar_check(disp, images[0], images[1], self._epi_K, self.shape, self._d_epi[0],
+                                   self._d_epi[1] if self.epi["map"] else None, scratch=self._epi_scratch,
+                                   **{k: v for k, v in self.epi.items() if k != "map"})
             Ts = None
             if self.motion is not None or self.ego is not None:
                 Ts = self.runner.last.get("Ts")  # None: the frame has no field (first of a sequence) -- roll only
@@ -526,6 +643,9 @@ class LiveSession:
                 if self.align_target is not None:
                     for host, dev_buf in zip(self._h_align[k], self._d_align):
                         host.copy_(dev_buf, non_blocking=True)
+                if self.epi is not None:
+                    for host, dev_buf in zip(self._h_epi[k], self._d_epi):
+                        host.copy_(dev_buf, non_blocking=True)
                 self._e_down[k].record(self._s_down)
         self._inflight.append(k)
         self._pushed += 1
@@ -545,6 +665,9 @@ class LiveSession:
         if self.align_target is not None:
             got = [t.numpy().copy() for t in self._h_align[k]]
             out.append(Aligned(got[0], got[1] if self.align["uv"] else None))
+        if self.epi is not None:
+            got = [t.numpy().copy() for t in self._h_epi[k]]
+            out.append(epipolar_from_record(got[0], got[1] if self.epi["map"] else None))
         return out[0] if len(out) == 1 else tuple(out)
 
     def _collect_ego(self, k):
@@ -559,7 +682,8 @@ class LiveSession:
     def pop(self):
         """The oldest frame's result: numpy [h,w] (fp32, or uint16 for ``disp_u16``), owned by the caller; with a
         ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None; with ``egomotion``, an ``Ego`` or None
-        follows; with ``confidence``, a ``Confidence``; with ``align_to``, an ``Aligned`` comes last."""
+        follows; with ``confidence``, a ``Confidence``; with ``align_to``, an ``Aligned``; with ``epipolar``, an
+        ``Epipolar`` comes last."""
         if self._ready:
             return self._ready.popleft()
         if not self._inflight:
@@ -589,7 +713,8 @@ class LiveSession:
             torch.cuda.current_stream(self.dev).synchronize()
             self._s_down.synchronize()
             for name in ("_h_in", "_d_in", "_scratch", "_maps", "_d_out", "_h_out", "_depth_prev", "_d_mot", "_h_mot",
-                         "_d_ego", "_h_ego", "_ego_scratch", "_d_conf", "_h_conf", "_d_align", "_h_align"):
+                         "_d_ego", "_h_ego", "_ego_scratch", "_d_conf", "_h_conf", "_d_align", "_h_align",
+                         "_d_epi", "_h_epi", "_epi_scratch"):
                 setattr(self, name, None)
             self._open_done = False
         self._inflight.clear()

@@ -2041,6 +2041,47 @@ def export_confidence(disp, flags, residual=None, left=None, right=None, crop=No
     return flags
 
 
+def epipolar_scratch(h, w):
+    """Bytes of scratch ``epipolar_check`` needs for an h x w crop (codd_epipolar_scratch)."""
+    n = int(_abi.load().codd_epipolar_scratch(int(h), int(w)))
+    if n <= 0:
+        raise ValueError(f"epipolar_scratch: positive (h, w) with h w < 2^31 expected, got {(h, w)}")
+    return n
+
+
+def epipolar_check(disp, left, right, K, shape, record, dy_map=None, scratch=None, range_px=2, step=2, tau=24.0,
+                   min_curv=0.5, iters=4, delta_px=0.25, min_valid=256, std=IMAGENET_STD):
+    """Is the rig still rectified?  Per measured pixel (every ``step``-th column and row) of the ``shape`` (h, w) crop the
+    row offset ``dy`` at which the normalised ``right`` image [3,H,W] (or [1,3,H,W]) really matches ``left`` under the padded
+    disparity ``disp`` [H,W] (or [1,1,H,W]) -- ``L(x, y) ~ R(x - d, y + dy)``, searched over ``-range_px .. range_px`` rows
+    -- and a robust fit ``dy = fy (c0 (1 + yn^2) + c1 xr yn + c2 xr + c3 yn)`` of that map with ``K`` = (fx, fy, cx, cy): a
+    rotation of the right view by (-c0, c1, c2) radians and a focal error c3 (include/codd_hip.h, codd_epipolar_check).
+    Outputs are caller-owned device tensors: ``record`` float64 [32] (c, ok, measurable, inliers, rms of dy, rms of the
+    inliers' residual, steps, the last step's A and b); ``dy_map`` fp32 [h,w] or None, NaN where nothing was measured.
+    ``scratch``: a uint8 tensor of ``epipolar_scratch(h, w)`` bytes; allocated here when None.  2 + iters launches on the
+    current stream, no host synchronisation."""
+    lib = _abi.load()
+    _require_gpu(disp)
+    H, W = disp.shape[-2:]
+    h, w = int(shape[0]), int(shape[1])
+    assert disp.dtype == torch.float32 and disp.is_cuda and disp.is_contiguous() and disp.numel() == H * W
+    for t in (left, right):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == 3 * H * W
+        assert tuple(t.shape[-3:]) == (3, H, W)
+    assert record.dtype == torch.float64 and record.is_cuda and record.is_contiguous() and record.numel() == 32
+    if dy_map is not None:
+        assert dy_map.dtype == torch.float32 and dy_map.is_cuda and dy_map.is_contiguous() and tuple(dy_map.shape) == (h, w)
+    if scratch is None:
+        scratch = torch.empty(epipolar_scratch(h, w), dtype=torch.uint8, device=disp.device)
+    assert scratch.dtype == torch.uint8 and scratch.is_cuda and scratch.is_contiguous()
+    _abi.check(lib.codd_epipolar_check(disp.data_ptr(), left.data_ptr(), right.data_ptr(), H, W, h, w, (C.c_float * 3)(*std),
+                                       *[float(v) for v in K], int(range_px), int(step), float(tau), float(min_curv),
+                                       int(iters), float(delta_px), int(min_valid), scratch.data_ptr(), scratch.numel(),
+                                       record.data_ptr(), None if dy_map is None else dy_map.data_ptr(), _stream()),
+               "epipolar_check")
+    return record
+
+
 ALIGN_MAX_FOOTPRINT = 4  # CODD_ALIGN_MAX_FOOTPRINT of include/codd_hip.h
 
 

@@ -808,6 +808,56 @@ int codd_export_confidence(const float* disp, const float* left, const float* ri
                            const float* stdv, float occ_px, float tau, unsigned char* flags, float* residual,
                            void* stream);
 
+/* Live-session rectification health check (codd_amd/live.py, epipolar=): the row offset at which the right image really
+ * matches the left one, per measured pixel, and a robust fit of that vertical-disparity map by a small rotation of the
+ * right view plus a focal ratio.  The reference has no such output; this replaces downloading the disparity and both
+ * images every frame and block matching on the host.  2 + iters launches (grey planes, measure, iters - 1 weighted passes,
+ * the statistics pass), no allocation, no host synchronisation.
+ * disp, left, right, stdv: as for codd_export_confidence (images and stdv required), read inside the h x w crop only.
+ * K = (fx, fy, cx, cy) of the rectified camera.  Every operation below is one fp32 operation rounded on its own (no
+ * fused multiply-add; division correctly rounded) unless it says fp64; x, y are the pixel's integer coordinates as floats.
+ *   grey     gL[y,x] = ((l0 * s0 + l1 * s1) + l2 * s2) * (1.f / 3.f), l_c = left[c,y,x], s_c = stdv[c]; gR likewise: grey
+ *            levels of the 8-bit source up to a constant that cancels in every difference.
+ *   measure  a pixel is measured iff x % step == 0 && y % step == 0 (step in 1 .. 8).  RX = 4, RY = 1, V = range_px in
+ *            1 .. 4.  d = disp[y,x]; u = x - d; f = floorf(u); a = u - f; b = 1.f - a.  The pixel is NOT MEASURABLE when d is
+ *            not finite or not > 0, or a tap leaves the crop: x - RX < 0, x + RX >= w, f - RX < 0, f + RX + 1 >= w,
+ *            y - RY - V < 0 or y + RY + V >= h.  Otherwise, for v = -V .. V,
+ *              R(r,i) = gR[y+r, f+i] * b + gR[y+r, f+i+1] * a                           (r = -RY-V .. RY+V, i = -RX .. RX)
+ *              row(v,j) = (..((|gL[y+j,x-RX] - R(j+v,-RX)| + |gL[y+j,x-RX+1] - R(j+v,-RX+1)|) + ..) + |gL[y+j,x+RX] - R(j+v,RX)|
+ *              C(v) = (row(v,-1) + row(v,0)) + row(v,1)
+ *            v* = the arg-min of C, ties to the smaller |v|, then to the smaller v (a C(v) that is NaN is never chosen
+ *            against C(0));  cm = C(v*-1), c0 = C(v*), cp = C(v*+1);  den = (cm - 2.f * c0) + cp.  Also NOT MEASURABLE: |v*| == V;
+ *            !(den > 27.f * min_curv) or !(den > 0) (no vertical texture);  !(c0 <= 27.f * tau) (a wrong match).
+ *            dy = (float)v* + (cm - cp) / (2.f * den):  L(x, y) ~ R(x - d, y + dy).
+ *   dy_map   fp32 [h,w], float alignment, may be NULL (the map then lives in the scratch): dy at measurable pixels, NaN at
+ *            every other pixel of the crop, measured or not.
+ *   model    xr = (u - cx) / fx;  yn = (y - cy) / fy;  p0 = fy * (1.f + yn * yn);  p1 = fy * (xr * yn);  p2 = fy * xr;
+ *            p3 = fy * yn;  e = dy - (((c0 * p0 + c1 * p1) + c2 * p2) + c3 * p3) with the fp64 coefficients rounded to fp32:
+ *            dy_model = fy (c0 (1 + yn^2) + c1 xr yn + c2 xr + c3 yn) is, to first order, a rotation of the right view by
+ *            (wx, wy, wz) = (-c0, c1, c2) radians, and c3 the relative focal error of the right view.
+ *   fit      c = 0; `iters` (1 .. 32) steps, each over the measurable pixels: wt = 1 in step 0 and 1.f / (1.f + (e * e) /
+ *            (delta_px * delta_px)) afterwards (Cauchy), e under the previous c;  q_i = wt * p_i;  A_ij = sum (double)(q_i *
+ *            p_j) (i <= j), b_i = sum (double)(q_i * dy), n = the number of measurable pixels: sums fp64 in a fixed order,
+ *            the products fp32;  c = A^-1 b by a 4x4 Cholesky in fp64.  Equal inputs give equal bits.  The fit stops with ok =
+ *            0 at the last good iterate (zeros if none) when n < min_valid, a Cholesky pivot (the diagonal entry before its
+ *            square root) is <= 1e-12 * trace(A), or a sum or a coefficient is not finite.
+ *   record   32 doubles, never NaN or infinite: [0:4] c, [4] ok, [5] n, [6] inliers (|e| <= delta_px under the final c),
+ *            [7] sqrt(sum (double)(dy * dy) / n) (0 for n = 0), [8] sqrt(sum (double)(e * e) over the inliers / inliers) (0
+ *            without inliers), [9] steps taken, [10:20] A of the last step (the sums the final c was solved from, or would
+ *            have been had the fit not stopped), upper triangle row by row, [20:24] its b -- an entry that is not finite is
+ *            written as 0 --, [24:32] zero.
+ * scratch: codd_epipolar_scratch(h, w) bytes (-1 for a non-positive size or h w >= 2^31), contents irrelevant, any
+ * alignment: the partial sums, both grey planes and the map (12 bytes per crop pixel).  The planes are read from global
+ * memory through the caches: no limit on w.
+ * CODD_EINVAL, before any launch: disp, left, right, stdv, scratch or record NULL; a non-positive size, h > H, w > W or
+ * h w >= 2^31; range_px outside [1, 4], step outside [1, 8], iters outside [1, 32]; fx, fy or delta_px not > 0; tau or
+ * min_curv NaN; scratch_bytes below the size function's answer. */
+long long codd_epipolar_scratch(int h, int w);
+int codd_epipolar_check(const float* disp, const float* left, const float* right, int H, int W, int h, int w,
+                        const float* stdv, float fx, float fy, float cx, float cy, int range_px, int step, float tau,
+                        float min_curv, int iters, float delta_px, int min_valid, void* scratch, long long scratch_bytes,
+                        double* record, float* dy_map, void* stream);
+
 /* Live-session depth on another camera's grid (codd_amd/live.py, align_to=): the frame's disparity, which lives on the
  * rectified virtual left camera, forward-warped into a calibrated target camera -- a physical camera of the rig or a
  * separate colour camera -- with occlusions resolved to the nearest surface.  The reference has no such output; this
