@@ -65,6 +65,17 @@ def parse_args(argv=None):
                         "vertical disparity: a rotation of the right view by (-c0, c1, c2) rad and a focal error c3), stats "
                         "[1, frames, 5] (ok, measurable, inliers, rms_px, rms_fit_px), A [1, frames, 4, 4] and b [1, frames, 4] "
                         "(each frame's normal equations), combined [4] and combined_ok (live.combine_epipolar over the video)")
+    p.add_argument("--ground", action="store_true",
+                   help="--live: find the floor; also write <name>.ground.pred.npz: coef [1, frames, 3] (the plane d = c0 (x - "
+                        "cx) + c1 (y - cy) + c2 in disparity space), ok [1, frames], normal [1, frames, 3] (from the floor to "
+                        "the camera), camera_height [1, frames] (unit of calib / fx), labels [1, frames, h, w] uint8 (0 floor, 1 "
+                        "obstacle, 2 overhead, 3 below, 255 invalid) and, with --ground-grid, grid_count [1, frames, 2, GH, GW] "
+                        "(floor and obstacle pixels per cell) and grid_height [1, frames, GH, GW]")
+    p.add_argument("--ground-height", type=float, default=None,
+                   help="--ground: the camera's mounting height above the floor (unit of calib / fx): seeds the fit")
+    p.add_argument("--ground-grid", default=None, metavar="GHxGW",
+                   help="--ground: also a top-down grid of GH rows (forward) x GW columns (right) on the floor")
+    p.add_argument("--ground-cell", type=float, default=None, help="--ground-grid: the side of a cell (default 0.1)")
     p.add_argument("--align-footprint", type=int, default=None, choices=[1, 2, 3, 4],
                    help="--align: target pixels per source pixel and axis (default: the smallest that leaves no hole lines)")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
@@ -114,6 +125,17 @@ def parse_args(argv=None):
         p.error("--occ-px / --tau need --confidence")
     if args.epipolar and not args.live:
         p.error("--epipolar needs --live")
+    if args.ground and not args.live:
+        p.error("--ground needs --live")
+    if (args.ground_height is not None or args.ground_grid is not None) and not args.ground:
+        p.error("--ground-height / --ground-grid need --ground")
+    if args.ground_grid is not None:
+        m = re.fullmatch(r"(\d+)x(\d+)", args.ground_grid)
+        if not m or not int(m.group(1)) or not int(m.group(2)):
+            p.error("--ground-grid: GHxGW expected")
+        args.ground_grid = (int(m.group(1)), int(m.group(2)))
+    elif args.ground_cell is not None:
+        p.error("--ground-cell needs --ground-grid")
     if args.align is not None:
         if not args.live:
             p.error("--align needs --live")
@@ -276,7 +298,9 @@ def run_live(args, model, videos):
     --confidence, <name>.conf.pred.npz (flags and residual, [1, frames, h, w] each) and, with --align,
     <name>.aligned.pred.npz (depth, [1, frames, ht, wt] on the target camera's grid) and, with --epipolar,
     <name>.epi.pred.npz (per-frame coefficients, counts, rms and normal equations plus the combined coefficients; one line
-    with the rms vertical disparity and the combined rotation is printed with or without --show).  With --pixel-format the
+    with the rms vertical disparity and the combined rotation is printed with or without --show) and, with --ground,
+    <name>.ground.pred.npz (per-frame plane, ok, normal, camera height and labels, and the grids with --ground-grid; one
+    line with the frames in which a floor was found is printed with or without --show).  With --pixel-format the
     frame files are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU.  With
     --calibration the frames (files or --frame-size) have the calibration's source size and every result has --net-size."""
     from PIL import Image
@@ -295,6 +319,11 @@ def run_live(args, model, videos):
             extra["align"] = dict(footprint=args.align_footprint)
     if getattr(args, "epipolar", False):
         extra["epipolar"] = True
+    if getattr(args, "ground", False):
+        g = dict(height=args.ground_height, grid=args.ground_grid)
+        if args.ground_cell is not None:
+            g["cell"] = args.ground_cell
+        extra["ground"] = g
     raw = getattr(args, "pixel_format", None)
     if raw:
         extra.update(pixel_format=raw, pitch=args.pitch, yuv=args.yuv or "bt601")
@@ -334,11 +363,15 @@ def run_live(args, model, videos):
             if align_to:
                 aligned = _NpzStream(osp.join(args.show_dir, name + ".aligned.pred.npz"), "depth",
                                      (1, nf) + s.align_target.camera.size, np.float32)
-        n, epis = 0, []
+        n, epis, grounds = 0, [], []
         try:
             frames = iter_raw_frames(lefts, rights, raw, src, args.pitch) if raw else iter_frames(lefts, rights)
             for res in live_results(s, frames):
                 n += 1
+                if "ground" in extra:
+                    res, g = res[:-1] if (args.motion or args.ego or args.confidence or align_to
+                                          or "epipolar" in extra) else res[0], res[-1]
+                    grounds.append(g if args.show else g._replace(labels=None, grid_count=None, grid_height=None))
                 if "epipolar" in extra:
                     res, ep = res[:-1] if (args.motion or args.ego or args.confidence or align_to) else res[0], res[-1]
                     epis.append(ep)
@@ -388,6 +421,21 @@ def run_live(args, model, videos):
             print(f"{name}: epipolar: rms vertical disparity {mean:.3f} px over {nv} pixels; combined rotation of the right "
                   f"view ({mdeg[0]:+.1f}, {mdeg[1]:+.1f}, {mdeg[2]:+.1f}) millidegrees, focal ratio {1 + coef[3]:.5f}"
                   f"{'' if ok else ' (not determined: too little texture)'}")
+        if "ground" in extra:
+            if args.show:
+                grids = {}
+                if args.ground_grid is not None:
+                    grids = dict(grid_count=np.array([[g.grid_count for g in grounds]]),
+                                 grid_height=np.array([[g.grid_height for g in grounds]]))
+                np.savez(osp.join(args.show_dir, name + ".ground.pred.npz"), coef=np.array([[g.coef for g in grounds]]),
+                         ok=np.array([[g.ok for g in grounds]]), normal=np.array([[g.normal for g in grounds]]),
+                         camera_height=np.array([[g.camera_height for g in grounds]]),
+                         labels=np.array([[g.labels for g in grounds]]), **grids)
+            good = [g for g in grounds if g.ok]
+            hs, ts = [g.camera_height for g in good], [g.tilt_deg for g in good]
+            print(f"{name}: ground: floor found in {len(good)} of {len(grounds)} frames"
+                  + (f"; camera height {np.mean(hs):.3f} (min {min(hs):.3f}, max {max(hs):.3f}), tilt against up "
+                     f"{np.mean(ts):.1f} degrees" if good else ""))
         print(f"{name}: {n} frames")
     for s in sessions.values():
         s.close()

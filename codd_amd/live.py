@@ -46,6 +46,11 @@ rig: ``codd_epipolar_check`` runs right after ``codd_export_confidence`` on the 
 measures per pixel the row offset at which the right image really matches, and fits a small rotation of the right view
 plus a focal ratio to that map; ``combine_epipolar`` pools the frames' normal equations and ``calibration.Rectification
 .corrected`` applies the result.  It needs no motion stage and no ``calibration=``.
+
+With ``ground=`` the session finds the floor: ``codd_ground_plane`` runs after the other export stages on the frame's
+disparity, fits one plane robustly in disparity space and returns per pixel the height above it and a label (floor,
+obstacle, overhead, below), plus, on request, a top-down grid of the floor and obstacle pixels a planner can read.  It
+needs no motion stage and no ``calibration=``.
 """
 from collections import deque, namedtuple
 
@@ -65,6 +70,9 @@ EGO_DEFAULTS = dict(iters=5, delta_px=1.0, tau_px=2.0, min_valid=16)
 CONF_DEFAULTS = dict(occ_px=1.0, tau=24.0)
 ALIGN_DEFAULTS = dict(footprint=None, uv=False)  # footprint None: calibration.auto_footprint
 EPI_DEFAULTS = dict(range_px=2, step=2, tau=24.0, min_curv=0.5, iters=4, delta_px=0.25, min_valid=256, map=False)
+GROUND_DEFAULTS = dict(step=2, iters=8, delta_px=0.25, delta0_px=4.0, asym=4.0, min_valid=256, max_tilt_deg=45.0, tol_px=0.5,
+                       ground_tol=0.05, clearance=2.0, height=None, pitch_deg=0.0, up=(0, -1, 0), map=False, grid=None,
+                       cell=0.1)
 
 # One frame's ego-motion, caller-owned: pose fp32 [7] = (t, q_xyzw) of G, the rigid motion that maps static points from
 # the previous camera frame to the current one (t in the unit of calib; the camera itself moved by G^-1); ok (False: the
@@ -106,6 +114,51 @@ def epipolar_from_record(rec, dy=None):
     A = A + np.triu(A, 1).T
     return Epipolar(rec[0:4].copy(), bool(rec[4] != 0), int(rec[5]), int(rec[6]), float(rec[7]), float(rec[8]), A,
                     rec[20:24].copy(), dy)
+
+
+# One frame's ground plane, caller-owned: coef float64 [3] of the fitted plane d = c0 (x - cx) + c1 (y - cy) + c2 in
+# disparity space; ok (False: no floor was found -- the fit was degenerate, tilted by more than max_tilt_deg against up,
+# had too few inliers, or the camera looks straight down -- and labels are all 255, heights NaN, grids zero); normal
+# float64 [3], the unit normal from the floor towards the camera in camera coordinates; camera_height above the plane and
+# every height in the unit of calib / fx (metres for a metric baseline); tilt_deg between normal and up; forward float64
+# [3], the grid's forward axis (the optical axis projected onto the plane); valid fit pixels, inliers (|e| <= delta_px)
+# and their rms_px; steps taken; labels uint8 [h,w] (0 floor, 1 obstacle, 2 overhead, 3 below the floor, 255 invalid);
+# height fp32 [h,w] above the plane, NaN where invalid (None unless ground=dict(map=True)); grid_count int32 [2,gh,gw]
+# (floor and obstacle pixels per cell) and grid_height fp32 [gh,gw] (the tallest obstacle pixel of a cell, 0 without one),
+# None unless ground=dict(grid=(gh, gw)): row iz = 0 lies under the camera, iz grows forward, column gw / 2 is straight
+# ahead and ix grows to the right, cells of `cell` units.
+Ground = namedtuple("Ground", "coef ok normal camera_height tilt_deg forward valid inliers rms_px steps labels height "
+                              "grid_count grid_height")
+
+
+def ground_from_record(rec, labels, height=None, grid_count=None, grid_height=None):
+    """The 32 doubles of codd_ground_plane (include/codd_hip.h) and its maps -> ``Ground``."""
+    rec = np.asarray(rec, np.float64)
+    return Ground(rec[0:3].copy(), bool(rec[3] != 0), rec[8:11].copy(), float(rec[11]), float(rec[12]), rec[22:25].copy(),
+                  int(rec[4]), int(rec[5]), float(rec[6]), int(rec[7]), labels, height, grid_count, grid_height)
+
+
+def _unit_up(up, pitch_deg=0.0):
+    """The unit up vector in camera coordinates after pitching the camera DOWN by ``pitch_deg`` (a rotation about the
+    camera's x axis: a level camera's (0, -1, 0) becomes (0, -cos, -sin))."""
+    u = np.array([float(v) for v in up], np.float64)
+    n = float(np.sqrt(u @ u))
+    if u.shape != (3,) or not (n > 0 and np.isfinite(n)):
+        raise ValueError(f"up: three finite numbers, not all zero, expected, got {up!r}")
+    u = u / n
+    t = np.deg2rad(float(pitch_deg))
+    return np.array([u[0], u[1] * np.cos(t) - u[2] * np.sin(t), u[1] * np.sin(t) + u[2] * np.cos(t)])
+
+
+def ground_seed(height, K, calib, up=(0, -1, 0), pitch_deg=0.0):
+    """The coefficients (float64 [3]) of the floor a camera mounted ``height`` above it sees: the plane N.X = calib with
+    N = -(calib / height) u, u the unit up vector after the pitch (``_unit_up``), is c = -(calib / height) (u_x / fx,
+    u_y / fy, u_z).  ``height`` is in the unit of calib / fx."""
+    if not (float(height) > 0 and np.isfinite(float(height))):
+        raise ValueError(f"ground_seed: a positive height expected, got {height!r}")
+    fx, fy = float(K[0]), float(K[1])
+    u = _unit_up(up, pitch_deg)
+    return -(float(calib) / float(height)) * np.array([u[0] / fx, u[1] / fy, u[2]])
 
 
 def solve_epipolar(A, b):
@@ -249,6 +302,64 @@ def _check_epi(epipolar):
     return p
 
 
+def _check_ground(ground):
+    """False / None -> None; True -> the defaults; a dict overrides them.  ValueError otherwise (no device call)."""
+    if ground is None or ground is False:
+        return None
+    if ground is True:
+        return dict(GROUND_DEFAULTS)
+    if not isinstance(ground, dict):
+        raise ValueError(f"ground: False, True or a dict of {tuple(GROUND_DEFAULTS)} expected, got {ground!r}")
+    unknown = set(ground) - set(GROUND_DEFAULTS)
+    if unknown:
+        raise ValueError(f"ground: unknown keys {sorted(unknown)}; known: {tuple(GROUND_DEFAULTS)}")
+    p = dict(GROUND_DEFAULTS, **ground)
+    is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+    for k, lo, hi in (("step", 1, 8), ("iters", 1, 32)):
+        if not (is_int(p[k]) and lo <= p[k] <= hi):
+            raise ValueError(f"ground: an integer {k} in [{lo}, {hi}] expected, got {p[k]!r}")
+    if not is_int(p["min_valid"]):
+        raise ValueError(f"ground: an integer min_valid expected, got {p['min_valid']!r}")
+    for k in ("delta_px", "delta0_px", "asym", "max_tilt_deg", "tol_px", "ground_tol", "clearance", "pitch_deg", "cell"):
+        try:
+            p[k] = float(p[k])
+        except (TypeError, ValueError):
+            raise ValueError(f"ground: a number expected for {k}, got {p[k]!r}") from None
+        if not np.isfinite(p[k]):
+            raise ValueError(f"ground: a finite {k} expected, got {p[k]!r}")
+    for k in ("delta_px", "delta0_px", "cell"):
+        if not p[k] > 0:
+            raise ValueError(f"ground: positive {k} expected, got {p[k]!r}")
+    if not p["asym"] >= 1:
+        raise ValueError(f"ground: asym >= 1 expected, got {p['asym']!r}")
+    for k in ("max_tilt_deg", "tol_px", "ground_tol"):
+        if not p[k] >= 0:
+            raise ValueError(f"ground: {k} >= 0 expected, got {p[k]!r}")
+    if not p["clearance"] >= p["ground_tol"]:
+        raise ValueError(f"ground: clearance >= ground_tol expected, got {p['clearance']!r} < {p['ground_tol']!r}")
+    if p["height"] is not None:
+        try:
+            p["height"] = float(p["height"])
+        except (TypeError, ValueError):
+            raise ValueError(f"ground: height None or a number expected, got {p['height']!r}") from None
+        if not (p["height"] > 0 and np.isfinite(p["height"])):
+            raise ValueError(f"ground: a positive height expected, got {p['height']!r}")
+    try:
+        p["up"] = tuple(float(v) for v in p["up"])
+        _unit_up(p["up"])
+    except (TypeError, ValueError):
+        raise ValueError(f"ground: up: three finite numbers, not all zero, expected, got {p['up']!r}") from None
+    if not isinstance(p["map"], bool):
+        raise ValueError(f"ground: map True or False expected, got {p['map']!r}")
+    if p["grid"] is not None:
+        g = p["grid"]
+        if not (isinstance(g, (tuple, list)) and len(g) == 2 and all(is_int(v) and v > 0 for v in g)
+                and g[0] * g[1] < 2 ** 30):
+            raise ValueError(f"ground: grid None or positive integers (gh, gw) with gh gw < 2^30 expected, got {g!r}")
+        p["grid"] = (g[0], g[1])
+    return p
+
+
 def _check_align(align, align_to):
     """None -> the defaults; a dict overrides them.  ValueError otherwise, and for ``align`` without ``align_to``."""
     if align is None:
@@ -379,7 +490,7 @@ class LiveSession:
 
     ``egomotion`` (False, True, or a dict overriding ``iters``, ``delta_px``, ``tau_px``, ``min_valid``): ``pop`` and
     ``step`` also return an ``Ego`` (or None for a frame without a field).  The tuple order is fixed:
-    ``result[, motion][, ego][, confidence][, aligned][, epipolar]``, each part present iff requested.
+    ``result[, motion][, ego][, confidence][, aligned][, epipolar][, ground]``, each part present iff requested.
 
     ``confidence`` (False, True, or a dict overriding ``occ_px`` (1.0 pixel) and ``tau`` (24.0 grey levels)): ``pop`` and
     ``step`` also return a ``Confidence(flags, residual)`` on the CURRENT frame's grid, for every frame (never None).  It
@@ -417,12 +528,26 @@ class LiveSession:
     per pixel and the cost's curvature across rows exceeds ``min_curv``; ``iters`` (1 .. 32) re-weighted steps with the
     Cauchy scale ``delta_px``; fewer than ``min_valid`` pixels make ``ok`` False; ``map`` True also returns the per-pixel
     ``dy``.  It needs no motion stage and no ``calibration=``.  Defined in include/codd_hip.h (codd_epipolar_check).
+
+    ``ground`` (False, True, or a dict overriding ``GROUND_DEFAULTS``): ``pop`` and ``step`` also return a ``Ground``, for
+    every frame (never None), last in the tuple: the floor plane fitted to the frame's disparity (``coef``, ``normal``,
+    ``camera_height``), per-pixel ``labels`` (0 floor, 1 obstacle, 2 overhead, 3 below, 255 invalid) and, on request, the
+    per-pixel ``height`` above the floor (``map`` True) and a top-down obstacle grid (``grid`` (gh, gw) cells of ``cell``
+    units; row 0 under the camera, rows forward, column gw / 2 straight ahead).  The fit runs over every ``step``-th (1 .. 8)
+    column and row in ``iters`` (1 .. 32) re-weighted steps whose Cauchy scale anneals from ``delta0_px`` to ``delta_px``
+    and is ``asym`` times tighter above the plane than below it, so that the floor is the lower envelope; ``height``
+    (the camera's mounting height) with ``pitch_deg`` (positive: looking down) and ``up`` seeds it (``ground_seed``),
+    without it the first step takes the lower half of the image; fewer than ``min_valid`` fit pixels or inliers, or a
+    plane tilted by more than ``max_tilt_deg`` against the pitched ``up``, make ``ok`` False -- then no pixel is labelled.
+    A pixel within ``tol_px`` of disparity or ``ground_tol`` of height of the plane is floor; above it, up to
+    ``clearance``, an obstacle.  Heights are in the unit of ``calib`` / fx.  It needs no motion stage and no
+    ``calibration=``; it uses the session's ``intrinsics`` and ``calib``.  Defined in include/codd_hip.h (codd_ground_plane).
     """
 
     def __init__(self, estimator, shape, intrinsics=None, calib=None, output="depth",
                  bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False,
                  pixel_format="rgb8", yuv="bt601", pitch=None, calibration=None, zoom=1.0, align_to=None, align=None,
-                 epipolar=False):
+                 epipolar=False, ground=False):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
@@ -434,6 +559,7 @@ class LiveSession:
             raise ValueError(f"egomotion={egomotion!r} needs an estimator with a motion stage (this one has none)")
         self.conf = _check_conf(confidence)
         self.epi = _check_epi(epipolar)
+        self.ground = _check_ground(ground)
         h, w = int(shape[0]), int(shape[1])
         if h <= 0 or w <= 0:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
@@ -465,6 +591,12 @@ class LiveSession:
                 self.align["footprint"] = _calibration.auto_footprint(R, self.align_target.camera, (h, w), self._align_K,
                                                                       r2_max=self._align_view.r2_max)
         self._epi_K = tuple(float(v) for v in intrinsics)
+        if self.ground is not None:
+            g = self.ground
+            self._ground_up = tuple(_unit_up(g["up"], g["pitch_deg"]))  # (the mount's pitch turns the expected normal too)
+            self._ground_seed = None if g["height"] is None else ground_seed(g["height"], self._epi_K, calib, g["up"],
+                                                                             g["pitch_deg"])
+            self._ground_par = {k: g[k] for k in ops.GROUND_PARAMS}
         self.src_shape = (h, w) if self.rect is None else self.rect.size  # the size of a frame as the camera hands it out
         # (rows, row_bytes, pitch, nbytes) of a source frame; ValueError if invalid
         self._layout = frame_layout(pixel_format, self.src_shape[0], self.src_shape[1], pitch)
@@ -543,6 +675,18 @@ class LiveSession:
                 self._h_epi = [tuple(torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_epi)
                                for _ in range(DEPTH)]
                 self._epi_scratch = torch.empty(ops.epipolar_scratch(h, w), dtype=torch.uint8, device=dev)
+            if self.ground is not None:
+                grid = self.ground["grid"]
+                self._d_ground = [torch.zeros(32, dtype=torch.float64, device=dev),
+                                  torch.empty(h, w, dtype=torch.uint8, device=dev)]
+                if self.ground["map"]:
+                    self._d_ground.append(torch.empty(h, w, dtype=torch.float32, device=dev))
+                if grid is not None:
+                    self._d_ground += [torch.empty((2,) + grid, dtype=torch.int32, device=dev),
+                                       torch.empty(grid, dtype=torch.float32, device=dev)]
+                self._h_ground = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_ground]
+                                  for _ in range(DEPTH)]
+                self._ground_scratch = torch.empty(ops.ground_scratch(h, w, grid), dtype=torch.uint8, device=dev)
             self._s_up, self._s_down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             ev = lambda: [torch.cuda.Event() for _ in range(DEPTH)]  # noqa: E731
             self._e_up, self._e_ingest, self._e_export, self._e_down = ev(), ev(), ev(), ev()
@@ -613,6 +757,10 @@ class LiveSession:
                 ops.epipolar_check(disp, images[0], images[1], self._epi_K, self.shape, self._d_epi[0],
                                    self._d_epi[1] if self.epi["map"] else None, scratch=self._epi_scratch,
                                    **{k: v for k, v in self.epi.items() if k != "map"})
+            if self.ground is not None:
+                ops.ground_plane(disp, self._epi_K, self.calib, self.shape, *self._ground_bufs(self._d_ground),
+                                 scratch=self._ground_scratch, seed=self._ground_seed, up=self._ground_up,
+                                 **self._ground_par)
             Ts = None
             if self.motion is not None or self.ego is not None:
                 Ts = self.runner.last.get("Ts")  # None: the frame has no field (first of a sequence) -- roll only
@@ -646,6 +794,9 @@ class LiveSession:
                 if self.epi is not None:
                     for host, dev_buf in zip(self._h_epi[k], self._d_epi):
                         host.copy_(dev_buf, non_blocking=True)
+                if self.ground is not None:
+                    for host, dev_buf in zip(self._h_ground[k], self._d_ground):
+                        host.copy_(dev_buf, non_blocking=True)
                 self._e_down[k].record(self._s_down)
         self._inflight.append(k)
         self._pushed += 1
@@ -668,7 +819,15 @@ class LiveSession:
         if self.epi is not None:
             got = [t.numpy().copy() for t in self._h_epi[k]]
             out.append(epipolar_from_record(got[0], got[1] if self.epi["map"] else None))
+        if self.ground is not None:
+            out.append(ground_from_record(*self._ground_bufs([t.numpy().copy() for t in self._h_ground[k]])))
         return out[0] if len(out) == 1 else tuple(out)
+
+    def _ground_bufs(self, bufs):
+        """(record, labels, height, grid_count, grid_height) of the buffers present, None for the others."""
+        rest = list(bufs[2:])
+        height = rest.pop(0) if self.ground["map"] else None
+        return (bufs[0], bufs[1], height) + (tuple(rest) if self.ground["grid"] is not None else (None, None))
 
     def _collect_ego(self, k):
         if not self._has_ego[k]:
@@ -683,7 +842,7 @@ class LiveSession:
         """The oldest frame's result: numpy [h,w] (fp32, or uint16 for ``disp_u16``), owned by the caller; with a
         ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None; with ``egomotion``, an ``Ego`` or None
         follows; with ``confidence``, a ``Confidence``; with ``align_to``, an ``Aligned``; with ``epipolar``, an
-        ``Epipolar`` comes last."""
+        ``Epipolar``; with ``ground``, a ``Ground`` comes last."""
         if self._ready:
             return self._ready.popleft()
         if not self._inflight:
@@ -714,7 +873,7 @@ class LiveSession:
             self._s_down.synchronize()
             for name in ("_h_in", "_d_in", "_scratch", "_maps", "_d_out", "_h_out", "_depth_prev", "_d_mot", "_h_mot",
                          "_d_ego", "_h_ego", "_ego_scratch", "_d_conf", "_h_conf", "_d_align", "_h_align",
-                         "_d_epi", "_h_epi", "_epi_scratch"):
+                         "_d_epi", "_h_epi", "_epi_scratch", "_d_ground", "_h_ground", "_ground_scratch"):
                 setattr(self, name, None)
             self._open_done = False
         self._inflight.clear()

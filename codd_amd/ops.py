@@ -2082,6 +2082,67 @@ def epipolar_check(disp, left, right, K, shape, record, dy_map=None, scratch=Non
     return record
 
 
+GROUND_FLOOR, GROUND_OBSTACLE, GROUND_OVERHEAD, GROUND_BELOW, GROUND_INVALID = 0, 1, 2, 3, 255  # CODD_GROUND_* of the header
+GROUND_PARAMS = dict(step=2, iters=8, delta_px=0.25, delta0_px=4.0, asym=4.0, min_valid=256, max_tilt_deg=45.0, tol_px=0.5,
+                     ground_tol=0.05, clearance=2.0, cell=0.1)
+
+
+def ground_scratch(h, w, grid=None):
+    """Bytes of scratch ``ground_plane`` needs for an h x w crop and a ``grid`` (gh, gw) or None (codd_ground_scratch)."""
+    gh, gw = (0, 0) if grid is None else (int(grid[0]), int(grid[1]))
+    n = int(_abi.load().codd_ground_scratch(int(h), int(w), gh, gw))
+    if n <= 0:
+        raise ValueError(f"ground_scratch: positive (h, w) with h w < 2^31 and a grid of None or positive (gh, gw) with "
+                         f"gh gw < 2^30 expected, got {(h, w)}, {grid}")
+    return n
+
+
+def ground_plane(disp, K, calib, crop, record, labels, height=None, grid_count=None, grid_height=None, scratch=None,
+                 seed=None, up=(0.0, -1.0, 0.0), **par):
+    """Where is the floor?  A robust fit of one plane ``d = c0 (x - cx) + c1 (y - cy) + c2`` to the ``crop`` (h, w) of the
+    padded disparity ``disp`` [H,W] (or [1,1,H,W]) with ``K`` = (fx, fy, cx, cy) and ``calib`` = fx * baseline, per pixel the
+    height above that plane and a label (GROUND_*), and a top-down grid of the floor and obstacle pixels
+    (include/codd_hip.h, codd_ground_plane).  Outputs are caller-owned device tensors: ``record`` float64 [32] (c, ok, fit
+    pixels, inliers, rms, steps, normal, camera height, tilt, the last step's A and b, the forward axis); ``labels`` uint8
+    [h,w]; ``height`` fp32 [h,w] or None; ``grid_count`` int32 [2,gh,gw] and ``grid_height`` fp32 [gh,gw], both or
+    neither.  ``seed``: three coefficients to start from (``live.ground_seed``) or None; ``up``: the unit up vector in
+    camera coordinates; ``par`` overrides ``GROUND_PARAMS``.  ``scratch``: a uint8 tensor of ``ground_scratch`` bytes;
+    allocated here when None.  iters + 1 launches on the current stream, no host synchronisation."""
+    lib = _abi.load()
+    _require_gpu(disp)
+    unknown = set(par) - set(GROUND_PARAMS)
+    if unknown:
+        raise TypeError(f"ground_plane: unknown parameters {sorted(unknown)}; known: {tuple(GROUND_PARAMS)}")
+    p = dict(GROUND_PARAMS, **par)
+    H, W = disp.shape[-2:]
+    h, w = int(crop[0]), int(crop[1])
+    assert disp.dtype == torch.float32 and disp.is_cuda and disp.is_contiguous() and disp.numel() == H * W
+    assert record.dtype == torch.float64 and record.is_cuda and record.is_contiguous() and record.numel() == 32
+    assert labels.dtype == torch.uint8 and labels.is_cuda and labels.is_contiguous() and tuple(labels.shape) == (h, w)
+    if height is not None:
+        assert height.dtype == torch.float32 and height.is_cuda and height.is_contiguous() and tuple(height.shape) == (h, w)
+    assert (grid_count is None) == (grid_height is None), "grid_count and grid_height: both or neither"
+    gh = gw = 0
+    if grid_count is not None:
+        gh, gw = (int(v) for v in grid_height.shape)
+        assert grid_height.dtype == torch.float32 and grid_height.is_cuda and grid_height.is_contiguous()
+        assert grid_count.dtype == torch.int32 and grid_count.is_cuda and grid_count.is_contiguous()
+        assert tuple(grid_count.shape) == (2, gh, gw)
+    if scratch is None:
+        scratch = torch.empty(ground_scratch(h, w, (gh, gw) if gh else None), dtype=torch.uint8, device=disp.device)
+    assert scratch.dtype == torch.uint8 and scratch.is_cuda and scratch.is_contiguous()
+    sd = None if seed is None else (C.c_double * 3)(*[float(v) for v in seed])
+    _abi.check(lib.codd_ground_plane(disp.data_ptr(), H, W, h, w, *[float(v) for v in K], float(calib), sd,
+                                     (C.c_float * 3)(*[float(v) for v in up]), int(p["step"]), int(p["iters"]),
+                                     float(p["delta_px"]), float(p["delta0_px"]), float(p["asym"]), int(p["min_valid"]),
+                                     float(p["max_tilt_deg"]), float(p["tol_px"]), float(p["ground_tol"]),
+                                     float(p["clearance"]), float(p["cell"]), gh, gw, scratch.data_ptr(), scratch.numel(),
+                                     record.data_ptr(), labels.data_ptr(), None if height is None else height.data_ptr(),
+                                     None if grid_count is None else grid_count.data_ptr(),
+                                     None if grid_height is None else grid_height.data_ptr(), _stream()), "ground_plane")
+    return record
+
+
 ALIGN_MAX_FOOTPRINT = 4  # CODD_ALIGN_MAX_FOOTPRINT of include/codd_hip.h
 
 

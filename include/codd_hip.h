@@ -904,6 +904,79 @@ int codd_align_depth(const float* disp, int H, int W, int h, int w, float f, flo
                      const codd_align_view* view, int ht, int wt, int footprint, float* depth_out, float* uv_out,
                      void* stream);
 
+/* Live-session ground plane (codd_amd/live.py, ground=): a robust fit of ONE plane to the frame's disparity, per pixel the
+ * height above it and a label, and a top-down grid of the floor and obstacle pixels in a frame that lies on the plane.  The
+ * reference has no such output; this replaces downloading the depth map every frame and a plane fit, a classification and
+ * a histogram on the host.  iters + 1 launches (iters weighted passes over the fit pixels -- the first also clears the grid
+ * -- and one pass over the whole crop), no allocation, no host synchronisation, no float atomics.
+ * disp [H,W]: the frame's padded disparity, read inside [0,h) x [0,w) only.  K = (fx, fy, cx, cy) of the rectified camera,
+ * calib = fx * baseline.  A pixel is VALID iff d = disp[y,x] is finite and > 0.
+ * The plane.  A 3-D plane N.X = calib, with X = Z ((x - cx) / fx, (y - cy) / fy, 1) and Z = calib / d, is  d = N.X d / calib =
+ * c0 (x - cx) + c1 (y - cy) + c2  with  N = (c0 fx, c1 fy, c2): in disparity space it is a plane too, and the noise of the fit
+ * is that of the measured quantity.  The camera sits at X = 0, at the distance Hc = calib / |N| from the plane; n = -N / |N|
+ * is the unit normal from the floor towards the camera; a point's height above the plane is n.X + Hc = Hc (1 - c.p / d) =
+ * Hc e / d with e the pixel's disparity residual.  An obstacle standing on the floor is nearer than the floor behind it:
+ * e > 0, and the floor is the LOWER envelope of the disparities.
+ * Every operation below is one fp32 operation rounded on its own (no fused multiply-add; division correctly rounded)
+ * unless it says fp64; x, y are the pixel's integer coordinates as floats.
+ *   terms    p0 = x - cx;  p1 = y - cy;  (p2 = 1);  e = d - ((c0 * p0 + c1 * p1) + c2) with the fp64 coefficients rounded to
+ *            fp32.
+ *   fit      over the FIT PIXELS: valid, x % step == 0 && y % step == 0 (step in 1 .. 8).  `iters` (1 .. 32) steps k = 0 ..
+ *            iters - 1, each under the previous c.  The scale anneals: s_k = max(delta_px, delta0_px * 0.5^k) (the product is
+ *            exact); s = e > 0 ? s_k / asym : s_k;  wt = 1.f / (1.f + (e * e) / (s * s)): an asymmetric Cauchy weight, asym >= 1
+ *            (1: symmetric).  Step 0 takes e under `seed` (HOST, 3 doubles) when it is given; with seed NULL step 0 uses
+ *            wt = 1 for y >= cy and wt = 0 above (the lower half of the image), and every later step is as above.
+ *            q0 = wt * p0, q1 = wt * p1;  A = sum of (double) of (q0 * p0, q0 * p1, q0, q1 * p1, q1, wt) (upper triangle row by
+ *            row), b = sum of (double) of (q0 * d, q1 * d, wt * d), n = the number of fit pixels (whatever their weight):
+ *            sums fp64 in a fixed order, the products fp32;  c = A^-1 b by a 3x3 Cholesky in fp64.  Equal inputs give equal
+ *            bits.  The fit stops with ok = 0 at the last good iterate (zeros if none: the seed is no iterate) when n <
+ *            min_valid, a Cholesky pivot (the diagonal entry before its square root) is <= 1e-12 * trace(A), or a sum or
+ *            a coefficient is not finite.
+ *   metric   fp64, from the final c, fx, fy, calib as doubles of the floats passed: N = (c0 fx, c1 fy, c2);  |N| = sqrt((N0 N0 +
+ *            N1 N1) + N2 N2);  Hc = calib / |N|;  n = -N / |N|;  tilt = acos(clamp((n0 u0 + n1 u1) + n2 u2, -1, 1)) in degrees,
+ *            u = `up` (HOST, 3 floats; the entry normalises it in fp64; image y points down, so a level camera has
+ *            up = (0, -1, 0));  g = z - (z.n) n = (-n2 n0, -n2 n1, 1 - n2 n2);  forward f = g / |g|;  right r = f x n.
+ *            ok = 0 as well when |N| is 0 or not finite or Hc is not finite (n, Hc, tilt, f stay 0); tilt > max_tilt_deg;
+ *            |g| < 1e-3 (the camera looks along the normal: no forward axis, f stays 0); or the inliers -- fit pixels with
+ *            |e| <= delta_px under the final c -- number fewer than min_valid.
+ *   pixel    over the WHOLE crop.  labels [h,w] bytes, any alignment; height fp32 [h,w], float alignment, may be NULL.
+ *            hgt = ((float)Hc * e) / d.  CODD_GROUND_INVALID: not valid (height NaN).  Otherwise, in this order:
+ *            CODD_GROUND_FLOOR iff |e| <= tol_px || |hgt| <= ground_tol;  CODD_GROUND_OVERHEAD iff hgt > clearance;
+ *            CODD_GROUND_OBSTACLE iff hgt > 0 (above the floor band, at most clearance);  CODD_GROUND_BELOW otherwise.
+ *            height = hgt, in the unit of calib / fx.  With ok = 0 every label is CODD_GROUND_INVALID, every height NaN and
+ *            the grid zero.
+ *   grid     optional (gh = gw = 0 and both pointers NULL: off).  Floor and obstacle pixels only:  Z = calib / d;  X0 = Z *
+ *            (p0 / fx);  X1 = Z * (p1 / fy);  gx = (r0 * X0 + r1 * X1) + r2 * Z;  gz = (f0 * X0 + f1 * X1) + f2 * Z with r, f, Hc
+ *            rounded to fp32;  ix = floorf(gx / cell + 0.5f * (float)gw);  iz = floorf(gz / cell);  a pixel outside [0, gw) x
+ *            [0, gh) (compared as floats; NaN is outside) is dropped.  The camera stands above the middle of row iz = 0;
+ *            iz grows forward, ix to the right.  grid_count int32 [2,gh,gw]: [0,iz,ix] floor pixels, [1,iz,ix] obstacle
+ *            pixels;  grid_height fp32 [gh,gw]: the largest hgt of the cell's obstacle pixels, 0 without one.  Counts
+ *            are integer atomic adds and the maximum an integer maximum over the bits of a positive float: equal inputs
+ *            give equal bytes.  The entry clears the grid on every call: nothing accumulates.
+ *   record   32 doubles, never NaN or infinite (an entry that is not finite is written as 0): [0:3] c, [3] ok, [4] fit pixels,
+ *            [5] inliers, [6] sqrt(sum (double)(e * e) over the inliers / inliers) (0 without inliers), [7] steps taken,
+ *            [8:11] n, [11] Hc, [12] tilt in degrees, [13:19] A of the last step (the sums the final c was solved from, or
+ *            would have been had the fit not stopped), upper triangle row by row, [19:22] its b, [22:25] f, [25:32] zero.
+ * scratch: codd_ground_scratch(h, w, gh, gw) bytes (-1 for a non-positive h or w, h w >= 2^31, a negative gh or gw, one of
+ * them 0 without the other, or gh gw >= 2^30), contents irrelevant, any alignment: the partial sums and the ticket.
+ * CODD_EINVAL, before any launch: disp, up, scratch, record or labels NULL; one grid pointer without the other; grid
+ * pointers without gh, gw > 0 and a finite cell > 0, or gh, gw != 0 without them; a non-positive size, h > H, w > W or
+ * h w >= 2^31; step outside [1, 8], iters outside [1, 32]; fx, fy, calib, delta_px or delta0_px not finite and > 0; cx or cy
+ * not finite; asym not finite and >= 1, or (delta_px / asym)^2 not > 0; max_tilt_deg, tol_px or ground_tol negative or
+ * NaN; clearance < ground_tol or NaN; cell NaN; up zero or not finite; a seed that is not finite; scratch_bytes below the
+ * size function's answer. */
+#define CODD_GROUND_FLOOR 0
+#define CODD_GROUND_OBSTACLE 1
+#define CODD_GROUND_OVERHEAD 2
+#define CODD_GROUND_BELOW 3
+#define CODD_GROUND_INVALID 255
+long long codd_ground_scratch(int h, int w, int gh, int gw);
+int codd_ground_plane(const float* disp, int H, int W, int h, int w, float fx, float fy, float cx, float cy, float calib,
+                      const double* seed, const float* up, int step, int iters, float delta_px, float delta0_px, float asym,
+                      int min_valid, float max_tilt_deg, float tol_px, float ground_tol, float clearance, float cell, int gh,
+                      int gw, void* scratch, long long scratch_bytes, double* record, unsigned char* labels, float* height,
+                      int* grid_count, float* grid_height, void* stream);
+
 /* Ablation plug-ins.  codd_fusion_select: mode 0 = KalmanFusion (model/fusion/others.py:124-153; constant
  * gain K = Q/(Q+R), the reference never updates P), mode 1 = GTFusion (:54-86; gt [B,1,hg,wg], zero-padded).
  * cur, warp, out: [B,1,H,W]. */
