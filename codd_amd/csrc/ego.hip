@@ -4,31 +4,24 @@
 // outputs["Ts"] (raft3d.py:268-270) writes with torch: dozens of launches over every pixel and a host sync for the 6x6
 // solve in every iteration.
 //
-// iters + 1 launches on one stream, a fixed grid of EGO_NB workgroups that stride over the crop:
+// iters + 1 launches on one stream, no allocation, no host synchronisation:
 //   pass 0          reads T (28 bytes / pixel) and depth_prev, writes X1 = T * X0 compactly (12 bytes / pixel) into the
 //                   caller's scratch and accumulates the L2 step's sums;
 //   pass k < iters  reads depth_prev and X1, accumulates the Cauchy-weighted sums under G_k;
 //   pass iters      the mask pass: residual flow and mask under the final G, and the inlier statistics.
-// Per-pixel terms are fp32, every sum over more than one pixel is fp64: lane -> wave butterfly -> LDS -> one partial row
-// per workgroup.  There is no finish launch between passes: every workgroup of pass k first adds pass k-1's EGO_NB rows in
-// index order (a fixed order: the same bits in every workgroup and in every run), solves the 6x6 and moves G itself.
-// Rows and the pose state are double-buffered by the parity of k, so no workgroup reads what another one of the same
-// launch writes.  The record needs sums of the mask pass itself: its workgroups take a ticket (one integer atomic, after a
-// device-scope fence) and the one that draws the last ticket adds the rows, again in index order.  No float atomics, no
-// grid barrier, no host synchronisation.
-#include "common.h"
+// The sums, the 6x6 solve and the ticket that picks the record's writer are fit_sums.h's scheme; a good step composes
+// the pose in fp64 and rounds it to fp32, which is what the per-pixel arithmetic uses.
+#include "fit_sums.h"
 #include "se3.h"
 
-#define EGO_NB 256     // workgroups of every pass: about one per CU of the MI355X, and the number of partial rows
 #define EGO_NS 20      // doubles per partial row: 17 sums of a Gauss-Newton pass (3 of the mask pass), padded
 #define EGO_STATE 16   // doubles per pose state: t, q, alive, steps
-#define EGO_PIVOT 1e-12
 
 struct EgoArgs {
   const float* T;
   const float* depth;
   float* x1;
-  double* partial;  // [2][EGO_NB][EGO_NS]
+  double* partial;  // [2][FIT_NB][EGO_NS]
   double* state;    // [2][EGO_STATE]
   unsigned* ticket;
   float* record;
@@ -73,48 +66,26 @@ __device__ void ego_apply(const double* xi, double* g) {
 
 // One Gauss-Newton step from the 17 sums s of a pass under the pose st (thread 0 only; A, b: LDS work arrays).
 // st: [0:7] the pose, rounded to fp32 (what the per-pixel arithmetic uses); [7] alive; [8] steps taken.
-__device__ void ego_step(const double* s, double* st, int min_valid, double* A, double* b) {
+__device__ void ego_step(const double* s, double* st, int min_valid, double (*A)[6], double* b) {
   if (st[7] == 0.0) return;  // stopped earlier: the last good iterate stays
   bool good = s[16] >= (double)min_valid;
   for (int i = 0; i < 17; ++i) good = good && fabs(s[i]) < (double)INFINITY;  // (false for NaN)
   if (good) {
-    for (int i = 0; i < 36; ++i) A[i] = 0.0;
+    for (int i = 0; i < 6; ++i)
+      for (int j = 0; j < 6; ++j) A[i][j] = 0.0;
     const double sw = s[0], ax = s[1], ay = s[2], az = s[3];
     const double tr = s[4] + s[7] + s[9];
-    A[0] = A[7] = A[14] = sw;
+    A[0][0] = A[1][1] = A[2][2] = sw;
     // -[a]x in the upper right block, its transpose below
-    A[0 * 6 + 4] = az; A[0 * 6 + 5] = -ay; A[1 * 6 + 3] = -az; A[1 * 6 + 5] = ax; A[2 * 6 + 3] = ay; A[2 * 6 + 4] = -ax;
-    A[4 * 6 + 0] = az; A[5 * 6 + 0] = -ay; A[3 * 6 + 1] = -az; A[5 * 6 + 1] = ax; A[3 * 6 + 2] = ay; A[4 * 6 + 2] = -ax;
-    A[3 * 6 + 3] = tr - s[4]; A[3 * 6 + 4] = -s[5]; A[3 * 6 + 5] = -s[6];
-    A[4 * 6 + 3] = -s[5]; A[4 * 6 + 4] = tr - s[7]; A[4 * 6 + 5] = -s[8];
-    A[5 * 6 + 3] = -s[6]; A[5 * 6 + 4] = -s[8]; A[5 * 6 + 5] = tr - s[9];
+    A[0][4] = az; A[0][5] = -ay; A[1][3] = -az; A[1][5] = ax; A[2][3] = ay; A[2][4] = -ax;
+    A[4][0] = az; A[5][0] = -ay; A[3][1] = -az; A[5][1] = ax; A[3][2] = ay; A[4][2] = -ax;
+    A[3][3] = tr - s[4]; A[3][4] = -s[5]; A[3][5] = -s[6];
+    A[4][3] = -s[5]; A[4][4] = tr - s[7]; A[4][5] = -s[8];
+    A[5][3] = -s[6]; A[5][4] = -s[8]; A[5][5] = tr - s[9];
     for (int i = 0; i < 6; ++i) b[i] = -s[10 + i];
-    const double floor_ = EGO_PIVOT * (3.0 * sw + 2.0 * tr);  // x trace(H)
-    // Cholesky in place (lower triangle), stopping at a pivot <= floor_
-    for (int j = 0; j < 6 && good; ++j) {
-      double d = A[j * 6 + j];
-      for (int k = 0; k < j; ++k) d -= A[j * 6 + k] * A[j * 6 + k];
-      if (!(d > floor_)) { good = false; break; }
-      const double l = sqrt(d);
-      A[j * 6 + j] = l;
-      for (int i = j + 1; i < 6; ++i) {
-        double v = A[i * 6 + j];
-        for (int k = 0; k < j; ++k) v -= A[i * 6 + k] * A[j * 6 + k];
-        A[i * 6 + j] = v / l;
-      }
-    }
+    good = fit_cholesky_solve<6>(A, b, FIT_PIVOT * (3.0 * sw + 2.0 * tr));  // x trace(H)
   }
   if (good) {
-    for (int i = 0; i < 6; ++i) {
-      double v = b[i];
-      for (int k = 0; k < i; ++k) v -= A[i * 6 + k] * b[k];
-      b[i] = v / A[i * 6 + i];
-    }
-    for (int i = 5; i >= 0; --i) {
-      double v = b[i];
-      for (int k = i + 1; k < 6; ++k) v -= A[k * 6 + i] * b[k];
-      b[i] = v / A[i * 6 + i];
-    }
     double g[7];
     for (int i = 0; i < 7; ++i) g[i] = st[i];
     ego_apply(b, g);
@@ -127,19 +98,6 @@ __device__ void ego_step(const double* s, double* st, int min_valid, double* A, 
   if (!good) st[7] = 0.0;
 }
 
-// columns [0, ncol) of the EGO_NB partial rows, added in index order: wave v takes columns v, v + 4, ..; lane l adds rows
-// l, l + 64, l + 128, l + 192, then a butterfly
-__device__ __forceinline__ void ego_sum_rows(const double* __restrict__ rows, int ncol, double* s) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int c = wave; c < ncol; c += 4) {
-    double v = 0.0;
-    for (int r = lane; r < EGO_NB; r += 64) v += rows[(size_t)r * EGO_NS + c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) s[c] = v;
-  }
-}
-
 __device__ __forceinline__ bool ego_finite3(V3 a) {
   return fabsf(a.x) < INFINITY && fabsf(a.y) < INFINITY && fabsf(a.z) < INFINITY;  // (false for NaN)
 }
@@ -150,14 +108,13 @@ __global__ __launch_bounds__(256) void ego_pass_kernel(EgoArgs a) {
   constexpr int NACC = PASS == 2 ? 3 : 17;
   __shared__ double sS[EGO_NS];
   __shared__ double sSt[EGO_STATE];
-  __shared__ double sA[36], sB[6];
+  __shared__ double sA[6][6], sB[6];
   __shared__ double sRed[NACC][4];
-  __shared__ unsigned sLast;
   const int tid = threadIdx.x;
 
   // ---- the pose of this pass: pass k-1's rows -> one Gauss-Newton step on top of pass k-1's pose
   if (PASS != 0) {
-    ego_sum_rows(a.partial + (size_t)((a.k - 1) & 1) * EGO_NB * EGO_NS, 17, sS);
+    fit_sum_rows<EGO_NS, 17>(a.partial + (size_t)((a.k - 1) & 1) * FIT_NB * EGO_NS, sS);
     __syncthreads();
     if (tid == 0) {
       if (a.k == 1) {
@@ -191,7 +148,7 @@ __global__ __launch_bounds__(256) void ego_pass_kernel(EgoArgs a) {
   const float d2 = a.delta * a.delta;
   // (a stopped fit needs no further sums; pass 0 and the mask pass always run)
   if (PASS != 1 || alive) {
-    for (long long e = (long long)blockIdx.x * 256 + tid; e < n; e += (long long)EGO_NB * 256) {
+    for (long long e = (long long)blockIdx.x * 256 + tid; e < n; e += (long long)FIT_NB * 256) {
       const int y = (int)(e / a.w), x = (int)(e - (long long)y * a.w);
       const size_t p = (size_t)y * a.W + x;
       const V3 X0 = inv_project(a.depth[p], x, y, a.fx, a.fy, a.cx, a.cy);
@@ -235,27 +192,12 @@ __global__ __launch_bounds__(256) void ego_pass_kernel(EgoArgs a) {
       }
     }
   }
-  const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int i = 0; i < NACC; ++i) {
-    double v = acc[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) sRed[i][wave] = v;
-  }
-  __syncthreads();
-  double* row = a.partial + ((size_t)(a.k & 1) * EGO_NB + blockIdx.x) * EGO_NS;
-  if (tid < NACC) row[tid] = sRed[tid][0] + sRed[tid][1] + sRed[tid][2] + sRed[tid][3];
+  fit_reduce_store<NACC>(acc, sRed, a.partial + ((size_t)(a.k & 1) * FIT_NB + blockIdx.x) * EGO_NS);
   if (PASS != 2) return;
 
   // ---- the record: the workgroup that draws the last ticket adds the mask pass's rows
-  __threadfence();  // this workgroup's row, device-wide, before its ticket
-  __syncthreads();
-  if (tid == 0) sLast = atomicAdd(a.ticket, 1u) == (unsigned)(EGO_NB - 1);
-  __syncthreads();
-  if (!sLast) return;
-  __threadfence();  // every other row, before they are read
-  ego_sum_rows(a.partial + (size_t)(a.k & 1) * EGO_NB * EGO_NS, 3, sS);
+  if (!fit_last_workgroup(a.ticket)) return;
+  fit_sum_rows<EGO_NS, 3>(a.partial + (size_t)(a.k & 1) * FIT_NB * EGO_NS, sS);
   __syncthreads();
   if (tid == 0) {
     float* rec = a.record;
@@ -270,12 +212,9 @@ __global__ __launch_bounds__(256) void ego_pass_kernel(EgoArgs a) {
   }
 }
 
-static inline long long ego_x1_offset() { return 8LL * (2 * EGO_NB * EGO_NS + 2 * EGO_STATE) + 16; }
-
 extern "C" long long codd_ego_motion_scratch(int h, int w) {
   if (h <= 0 || w <= 0) return -1;
-  // 16 bytes of slack (the call aligns the caller's pointer itself), rows + states, the ticket, X1
-  return 16 + ego_x1_offset() + 12LL * h * w;
+  return fit_scratch_bytes(EGO_NS, EGO_STATE) + 12LL * h * w;  // X1
 }
 
 extern "C" int codd_ego_motion(const float* T, const float* depth_prev, int H, int W, int h, int w, float fx, float fy,
@@ -287,22 +226,20 @@ extern "C" int codd_ego_motion(const float* T, const float* depth_prev, int H, i
   if (iters < 1 || iters > 32) return CODD_EINVAL;
   if (!(fx > 0.f) || !(fy > 0.f) || !(delta_px > 0.f) || !(tau_px > 0.f)) return CODD_EINVAL;
   if (scratch_bytes < codd_ego_motion_scratch(h, w)) return CODD_EINVAL;
-  char* base = (char*)(((uintptr_t)scratch + 15) & ~(uintptr_t)15);
+  const FitScratch f = fit_carve(scratch, EGO_NS, EGO_STATE);
   EgoArgs a;
   a.T = T; a.depth = depth_prev;
-  a.partial = (double*)base;
-  a.state = a.partial + 2 * EGO_NB * EGO_NS;
-  a.ticket = (unsigned*)(a.state + 2 * EGO_STATE);
-  a.x1 = (float*)(base + ego_x1_offset());
+  a.partial = f.partial; a.state = f.state; a.ticket = f.ticket;
+  a.x1 = (float*)f.rest;
   a.record = record; a.moving = moving; a.residual = residual;
   a.W = W; a.h = h; a.w = w; a.iters = iters; a.min_valid = min_valid;
   a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.scale = scale; a.delta = delta_px / fx; a.tau = tau_px;
   hipStream_t s = (hipStream_t)stream;
   for (int k = 0; k <= iters; ++k) {
     a.k = k;
-    if (k == 0) ego_pass_kernel<0><<<EGO_NB, 256, 0, s>>>(a);
-    else if (k < iters) ego_pass_kernel<1><<<EGO_NB, 256, 0, s>>>(a);
-    else ego_pass_kernel<2><<<EGO_NB, 256, 0, s>>>(a);
+    if (k == 0) ego_pass_kernel<0><<<FIT_NB, 256, 0, s>>>(a);
+    else if (k < iters) ego_pass_kernel<1><<<FIT_NB, 256, 0, s>>>(a);
+    else ego_pass_kernel<2><<<FIT_NB, 256, 0, s>>>(a);
     CODD_LAUNCH_CHECK();
   }
   return CODD_OK;

@@ -20,19 +20,14 @@
 // wave's taps are 10 consecutive floats per row and lane, `step` floats apart between lanes, where the disparity is smooth
 // -- the vector cache and the L2 serve the reuse, there is no width limit and no second code path.
 //
-// Sums follow ego.hip: per-pixel terms fp32, every sum over more than one pixel fp64, lane -> wave butterfly -> LDS -> one
-// partial row per workgroup of a fixed grid; every workgroup of pass k first adds pass k-1's rows in index order, solves the
-// 4x4 and moves c itself (rows and state double-buffered by the parity of k); the last pass's workgroups take a ticket
-// (one integer atomic behind a device-scope fence) and the one that draws the last adds the rows and writes the record.
-// No float atomics, no grid barrier.
-#include "common.h"
+// The sums of the measure and fit passes, the 4x4 solve and the ticket that picks the record's writer are fit_sums.h's
+// scheme.
+#include "fit_sums.h"
 
-#define EPI_NB 256     // workgroups of the measure and fit passes, and the number of partial rows
 #define EPI_NS 16      // doubles per partial row: A (10), b (4), n, sum dy^2; the last pass uses 4
 #define EPI_STATE 8    // doubles per state: c (4), alive, steps
 #define EPI_RX 4
 #define EPI_RY 1
-#define EPI_PIVOT 1e-12
 
 struct EpiArgs {
   const float* disp;
@@ -41,7 +36,7 @@ struct EpiArgs {
   float* gl;        // [h,w]
   float* gr;        // [h,w]
   float* map;       // [h,w]: the caller's dy_map, or the scratch
-  double* partial;  // [2][EPI_NB][EPI_NS]
+  double* partial;  // [2][FIT_NB][EPI_NS]
   double* state;    // [2][EPI_STATE]
   unsigned* ticket;
   double* record;
@@ -162,31 +157,9 @@ __device__ void epi_step(const double* s, double* st, int min_valid, double (*A)
     for (int i = 0; i < 4; ++i)
       for (int j = i; j < 4; ++j) A[j][i] = s[n++];  // the lower triangle
     for (int i = 0; i < 4; ++i) b[i] = s[10 + i];
-    const double floor_ = EPI_PIVOT * (A[0][0] + A[1][1] + A[2][2] + A[3][3]);
-    for (int j = 0; j < 4 && good; ++j) {  // Cholesky in place, stopping at a pivot <= floor_
-      double d = A[j][j];
-      for (int k = 0; k < j; ++k) d -= A[j][k] * A[j][k];
-      if (!(d > floor_)) { good = false; break; }
-      const double l = sqrt(d);
-      A[j][j] = l;
-      for (int i = j + 1; i < 4; ++i) {
-        double v = A[i][j];
-        for (int k = 0; k < j; ++k) v -= A[i][k] * A[j][k];
-        A[i][j] = v / l;
-      }
-    }
+    good = fit_cholesky_solve<4>(A, b, FIT_PIVOT * (A[0][0] + A[1][1] + A[2][2] + A[3][3]));
   }
   if (good) {
-    for (int i = 0; i < 4; ++i) {
-      double v = b[i];
-      for (int k = 0; k < i; ++k) v -= A[i][k] * b[k];
-      b[i] = v / A[i][i];
-    }
-    for (int i = 3; i >= 0; --i) {
-      double v = b[i];
-      for (int k = i + 1; k < 4; ++k) v -= A[k][i] * b[k];
-      b[i] = v / A[i][i];
-    }
     for (int i = 0; i < 4; ++i) good = good && fabs(b[i]) < (double)INFINITY;
     if (good) {
       for (int i = 0; i < 4; ++i) st[i] = b[i];
@@ -195,31 +168,6 @@ __device__ void epi_step(const double* s, double* st, int min_valid, double (*A)
   }
   if (!good) st[4] = 0.0;
 }
-
-// columns [0, NCOL) of the EPI_NB partial rows, added in index order (ego.hip's ego_sum_rows: wave v takes columns v, v + 4,
-// ..; lane l adds rows l, l + 64, l + 128, l + 192, then a butterfly).  The rows were written by the launch before, on other
-// XCDs: every load of a lane is requested before the first is used, so the wave waits for memory once, not once per column.
-template <int NCOL>
-__device__ __forceinline__ void epi_sum_rows(const double* __restrict__ rows, double* s) {
-  constexpr int NC = (NCOL + 3) / 4, NR = EPI_NB / 64;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double r[NC][NR];
-#pragma unroll
-  for (int i = 0; i < NC; ++i)
-#pragma unroll
-    for (int j = 0; j < NR; ++j) r[i][j] = rows[(size_t)(lane + 64 * j) * EPI_NS + (wave + 4 * i)];
-#pragma unroll
-  for (int i = 0; i < NC; ++i) {
-    double v = 0.0;
-#pragma unroll
-    for (int j = 0; j < NR; ++j) v += r[i][j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) s[wave + 4 * i] = v;
-  }
-}
-
-__device__ __forceinline__ double epi_clean(double v) { return fabs(v) < (double)INFINITY ? v : 0.0; }
 
 // V > 0: the measure pass (k = 0) with search range V; V = 0: a Cauchy-weighted pass; V = -1: the last pass
 template <int V>
@@ -230,7 +178,6 @@ __global__ __launch_bounds__(256) void epi_pass_kernel(EpiArgs a) {
   __shared__ double sA[4][4], sB[4];
   __shared__ double sSt[EPI_STATE];
   __shared__ double sRed[NACC][4];
-  __shared__ unsigned sLast;
   const int tid = threadIdx.x;
 
   // ---- the coefficients of this pass: pass k-1's rows -> one step on top of pass k-1's state
@@ -240,7 +187,7 @@ __global__ __launch_bounds__(256) void epi_pass_kernel(EpiArgs a) {
 #pragma unroll
       for (int i = 0; i < EPI_STATE; ++i) prev[i] = a.state[((a.k - 1) & 1) * EPI_STATE + i];
     }
-    epi_sum_rows<EPI_NS>(a.partial + (size_t)((a.k - 1) & 1) * EPI_NB * EPI_NS, sS);
+    fit_sum_rows<EPI_NS, EPI_NS>(a.partial + (size_t)((a.k - 1) & 1) * FIT_NB * EPI_NS, sS);
     __syncthreads();
     if (tid == 0) {
 #pragma unroll
@@ -267,7 +214,7 @@ __global__ __launch_bounds__(256) void epi_pass_kernel(EpiArgs a) {
   const int nx = (a.w + a.step - 1) / a.step, ny = (a.h + a.step - 1) / a.step;
   const long long n = (long long)nx * ny;
   const float d2 = a.delta * a.delta;
-  for (long long e = (long long)blockIdx.x * 256 + tid; e < n; e += (long long)EPI_NB * 256) {
+  for (long long e = (long long)blockIdx.x * 256 + tid; e < n; e += (long long)FIT_NB * 256) {
     const int gy = (int)(e / nx), gx = (int)(e - (long long)gy * nx);
     const int x = gx * a.step, y = gy * a.step;
     float dy;
@@ -290,27 +237,12 @@ __global__ __launch_bounds__(256) void epi_pass_kernel(EpiArgs a) {
       epi_accumulate(t, V > 0 ? 1.f : 1.f / (1.f + (t.e * t.e) / d2), dy, acc);
     }
   }
-  const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int i = 0; i < NACC; ++i) {
-    double v = acc[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) sRed[i][wave] = v;
-  }
-  __syncthreads();
-  double* row = a.partial + ((size_t)(a.k & 1) * EPI_NB + blockIdx.x) * EPI_NS;
-  if (tid < NACC) row[tid] = sRed[tid][0] + sRed[tid][1] + sRed[tid][2] + sRed[tid][3];
+  fit_reduce_store<NACC>(acc, sRed, a.partial + ((size_t)(a.k & 1) * FIT_NB + blockIdx.x) * EPI_NS);
   if (V != -1) return;
 
   // ---- the record: the workgroup that draws the last ticket adds the last pass's rows
-  __threadfence();  // this workgroup's row, device-wide, before its ticket
-  __syncthreads();
-  if (tid == 0) sLast = atomicAdd(a.ticket, 1u) == (unsigned)(EPI_NB - 1);
-  __syncthreads();
-  if (!sLast) return;
-  __threadfence();  // every other row, before they are read
-  epi_sum_rows<4>(a.partial + (size_t)(a.k & 1) * EPI_NB * EPI_NS, sF);
+  if (!fit_last_workgroup(a.ticket)) return;
+  fit_sum_rows<EPI_NS, 4>(a.partial + (size_t)(a.k & 1) * FIT_NB * EPI_NS, sF);
   __syncthreads();
   if (tid == 0) {
     double* rec = a.record;
@@ -318,20 +250,17 @@ __global__ __launch_bounds__(256) void epi_pass_kernel(EpiArgs a) {
     rec[4] = sSt[4] != 0.0 ? 1.0 : 0.0;
     rec[5] = sF[0];
     rec[6] = sF[2];
-    rec[7] = sF[0] > 0.0 ? epi_clean(sqrt(sF[1] / sF[0])) : 0.0;
-    rec[8] = sF[2] > 0.0 ? epi_clean(sqrt(sF[3] / sF[2])) : 0.0;
+    rec[7] = sF[0] > 0.0 ? fit_clean(sqrt(sF[1] / sF[0])) : 0.0;
+    rec[8] = sF[2] > 0.0 ? fit_clean(sqrt(sF[3] / sF[2])) : 0.0;
     rec[9] = sSt[5];
-    for (int i = 0; i < 14; ++i) rec[10 + i] = epi_clean(sS[i]);  // the last step's A (upper triangle) and b
+    for (int i = 0; i < 14; ++i) rec[10 + i] = fit_clean(sS[i]);  // the last step's A (upper triangle) and b
     for (int i = 24; i < 32; ++i) rec[i] = 0.0;
   }
 }
 
-static inline long long epi_planes_offset() { return 8LL * (2 * EPI_NB * EPI_NS + 2 * EPI_STATE) + 16; }
-
 extern "C" long long codd_epipolar_scratch(int h, int w) {
   if (h <= 0 || w <= 0 || (long long)h * w >= (1LL << 31)) return -1;
-  // 16 bytes of slack (the call aligns the caller's pointer itself), rows + states, the ticket, two grey planes, the map
-  return 16 + epi_planes_offset() + 12LL * h * w;
+  return fit_scratch_bytes(EPI_NS, EPI_STATE) + 12LL * h * w;  // two grey planes, the map
 }
 
 extern "C" int codd_epipolar_check(const float* disp, const float* left, const float* right, int H, int W, int h, int w,
@@ -343,14 +272,12 @@ extern "C" int codd_epipolar_check(const float* disp, const float* left, const f
   if (range_px < 1 || range_px > 4 || step < 1 || step > 8 || iters < 1 || iters > 32) return CODD_EINVAL;
   if (!(fx > 0.f) || !(fy > 0.f) || !(delta_px > 0.f) || tau != tau || min_curv != min_curv) return CODD_EINVAL;
   if (scratch_bytes < codd_epipolar_scratch(h, w)) return CODD_EINVAL;
-  char* base = (char*)(((uintptr_t)scratch + 15) & ~(uintptr_t)15);
+  const FitScratch f = fit_carve(scratch, EPI_NS, EPI_STATE);
   const size_t n = (size_t)h * w;
   EpiArgs a;
   a.disp = disp; a.left = left; a.right = right;
-  a.partial = (double*)base;
-  a.state = a.partial + 2 * EPI_NB * EPI_NS;
-  a.ticket = (unsigned*)(a.state + 2 * EPI_STATE);
-  a.gl = (float*)(base + epi_planes_offset());
+  a.partial = f.partial; a.state = f.state; a.ticket = f.ticket;
+  a.gl = (float*)f.rest;
   a.gr = a.gl + n;
   a.map = dy_map ? dy_map : a.gr + n;
   a.record = record;
@@ -365,16 +292,16 @@ extern "C" int codd_epipolar_check(const float* disp, const float* left, const f
   epi_grey_kernel<<<(unsigned)(gb < 2048 ? gb : 2048), 256, 0, s>>>(a);
   CODD_LAUNCH_CHECK();
   switch (range_px) {
-    case 1: epi_pass_kernel<1><<<EPI_NB, 256, 0, s>>>(a); break;
-    case 2: epi_pass_kernel<2><<<EPI_NB, 256, 0, s>>>(a); break;
-    case 3: epi_pass_kernel<3><<<EPI_NB, 256, 0, s>>>(a); break;
-    default: epi_pass_kernel<4><<<EPI_NB, 256, 0, s>>>(a); break;
+    case 1: epi_pass_kernel<1><<<FIT_NB, 256, 0, s>>>(a); break;
+    case 2: epi_pass_kernel<2><<<FIT_NB, 256, 0, s>>>(a); break;
+    case 3: epi_pass_kernel<3><<<FIT_NB, 256, 0, s>>>(a); break;
+    default: epi_pass_kernel<4><<<FIT_NB, 256, 0, s>>>(a); break;
   }
   CODD_LAUNCH_CHECK();
   for (int k = 1; k <= iters; ++k) {
     a.k = k;
-    if (k < iters) epi_pass_kernel<0><<<EPI_NB, 256, 0, s>>>(a);
-    else epi_pass_kernel<-1><<<EPI_NB, 256, 0, s>>>(a);
+    if (k < iters) epi_pass_kernel<0><<<FIT_NB, 256, 0, s>>>(a);
+    else epi_pass_kernel<-1><<<FIT_NB, 256, 0, s>>>(a);
     CODD_LAUNCH_CHECK();
   }
   return CODD_OK;

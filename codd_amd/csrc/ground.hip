@@ -10,11 +10,8 @@
 //   pass k < iters  reads disp at the fit pixels, accumulates the weighted sums under c_k (c_0: the seed); pass 0 also clears
 //                   the grid and the ticket, which the last pass -- a later launch -- uses;
 //   pass iters      over the whole crop: statistics under the final c, labels, heights and the grid scatter; the record.
-// Sums follow epipolar.hip: per-pixel terms fp32, every sum over more than one pixel fp64, lane -> wave butterfly -> LDS ->
-// one partial row per workgroup of a fixed grid; every workgroup of pass k first adds pass k-1's rows in index order, solves
-// the 3x3 and (last pass) derives the metric plane itself (rows and state double-buffered by the parity of k); the last
-// pass's workgroups take a ticket (one integer atomic behind a device-scope fence) and the one that draws the last adds
-// the rows and writes the record.  No float atomics, no grid barrier.
+// The sums, the 3x3 solve and the ticket that picks the record's writer are fit_sums.h's scheme; on top of it every
+// workgroup of the last pass derives the metric plane itself, and labels, heights and grid updates precede its ticket.
 //
 // The grid scatter: neighbouring pixels of a row mostly fall into the same cell (a near-field cell collects thousands of
 // pixels), so a lane-per-pixel atomic serialises on a few addresses.  The cells of a 128 x 128 grid (192 KiB with both
@@ -22,16 +19,14 @@
 // not bounded beforehand; so each wave first merges RUNS of equal cell indices among its 64 consecutive pixels -- a ballot
 // gives the run length, a segmented shuffle maximum the run's height -- and only a run's first lane issues the atomics.
 // Integer add and integer max do not depend on grouping or order: the bytes are those of one atomic per pixel.
-#include "common.h"
+#include "fit_sums.h"
 
-#define GND_NB 256    // workgroups of every pass, and the number of partial rows
 #define GND_NS 10     // doubles per partial row: A (6), b (3), n; the last pass uses 3
 #define GND_STATE 8   // doubles per state: c (3), alive, steps
-#define GND_PIVOT 1e-12
 
 struct GndArgs {
   const float* disp;
-  double* partial;  // [2][GND_NB][GND_NS]
+  double* partial;  // [2][FIT_NB][GND_NS]
   double* state;    // [2][GND_STATE]
   unsigned* ticket;
   double* record;
@@ -60,31 +55,9 @@ __device__ void gnd_step(const double* s, double* st, int min_valid, double (*A)
     for (int i = 0; i < 3; ++i)
       for (int j = i; j < 3; ++j) A[j][i] = s[n++];  // the lower triangle
     for (int i = 0; i < 3; ++i) b[i] = s[6 + i];
-    const double floor_ = GND_PIVOT * (A[0][0] + A[1][1] + A[2][2]);
-    for (int j = 0; j < 3 && good; ++j) {  // Cholesky in place, stopping at a pivot <= floor_
-      double d = A[j][j];
-      for (int k = 0; k < j; ++k) d -= A[j][k] * A[j][k];
-      if (!(d > floor_)) { good = false; break; }
-      const double l = sqrt(d);
-      A[j][j] = l;
-      for (int i = j + 1; i < 3; ++i) {
-        double v = A[i][j];
-        for (int k = 0; k < j; ++k) v -= A[i][k] * A[j][k];
-        A[i][j] = v / l;
-      }
-    }
+    good = fit_cholesky_solve<3>(A, b, FIT_PIVOT * (A[0][0] + A[1][1] + A[2][2]));
   }
   if (good) {
-    for (int i = 0; i < 3; ++i) {
-      double v = b[i];
-      for (int k = 0; k < i; ++k) v -= A[i][k] * b[k];
-      b[i] = v / A[i][i];
-    }
-    for (int i = 2; i >= 0; --i) {
-      double v = b[i];
-      for (int k = i + 1; k < 3; ++k) v -= A[k][i] * b[k];
-      b[i] = v / A[i][i];
-    }
     for (int i = 0; i < 3; ++i) good = good && fabs(b[i]) < (double)INFINITY;
     if (good) {
       for (int i = 0; i < 3; ++i) st[i] = b[i];
@@ -129,34 +102,6 @@ __device__ void gnd_metric(const GndArgs& a, const double* st, GndPlane* m) {
   m->ok = ok ? 1 : 0;
 }
 
-// columns [0, NCOL) of the GND_NB partial rows, added in index order (epipolar.hip's epi_sum_rows: wave v takes columns v,
-// v + 4, ..; lane l adds rows l, l + 64, l + 128, l + 192, then a butterfly); every load of a lane is requested before the
-// first is used.
-template <int NCOL>
-__device__ __forceinline__ void gnd_sum_rows(const double* __restrict__ rows, double* s) {
-  constexpr int NC = (NCOL + 3) / 4, NR = GND_NB / 64;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double r[NC][NR];
-#pragma unroll
-  for (int i = 0; i < NC; ++i)
-#pragma unroll
-    for (int j = 0; j < NR; ++j) {
-      const int col = wave + 4 * i;
-      r[i][j] = col < NCOL ? rows[(size_t)(lane + 64 * j) * GND_NS + col] : 0.0;
-    }
-#pragma unroll
-  for (int i = 0; i < NC; ++i) {
-    double v = 0.0;
-#pragma unroll
-    for (int j = 0; j < NR; ++j) v += r[i][j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0 && wave + 4 * i < NCOL) s[wave + 4 * i] = v;
-  }
-}
-
-__device__ __forceinline__ double gnd_clean(double v) { return fabs(v) < (double)INFINITY ? v : 0.0; }
-
 // LAST = false: a weighted pass k < iters over the fit pixels; LAST = true: pass iters over the whole crop
 template <bool LAST>
 __global__ __launch_bounds__(256) void gnd_pass_kernel(GndArgs a) {
@@ -167,8 +112,7 @@ __global__ __launch_bounds__(256) void gnd_pass_kernel(GndArgs a) {
   __shared__ double sSt[GND_STATE];
   __shared__ double sRed[NACC][4];
   __shared__ GndPlane sM;
-  __shared__ unsigned sLast;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
 
   // ---- the coefficients of this pass: pass k-1's rows -> one step on top of pass k-1's state
   if (a.k > 0) {
@@ -177,7 +121,7 @@ __global__ __launch_bounds__(256) void gnd_pass_kernel(GndArgs a) {
 #pragma unroll
       for (int i = 0; i < GND_STATE; ++i) prev[i] = a.state[((a.k - 1) & 1) * GND_STATE + i];
     }
-    gnd_sum_rows<GND_NS>(a.partial + (size_t)((a.k - 1) & 1) * GND_NB * GND_NS, sS);
+    fit_sum_rows<GND_NS, GND_NS>(a.partial + (size_t)((a.k - 1) & 1) * FIT_NB * GND_NS, sS);
     __syncthreads();
     if (tid == 0) {
 #pragma unroll
@@ -207,7 +151,7 @@ __global__ __launch_bounds__(256) void gnd_pass_kernel(GndArgs a) {
   if constexpr (!LAST) {
     if (a.k == 0 && a.grid_count) {  // the entry clears the grid itself: nothing accumulates over calls
       const int cells = a.gh * a.gw;
-      for (int i = blockIdx.x * 256 + tid; i < cells; i += GND_NB * 256) {
+      for (int i = blockIdx.x * 256 + tid; i < cells; i += FIT_NB * 256) {
         a.grid_count[i] = 0;
         a.grid_count[cells + i] = 0;
         a.grid_height[i] = 0;
@@ -216,7 +160,7 @@ __global__ __launch_bounds__(256) void gnd_pass_kernel(GndArgs a) {
     const int nx = (a.w + a.step - 1) / a.step, ny = (a.h + a.step - 1) / a.step;
     const long long n = (long long)nx * ny;
     const bool flat = a.k == 0 && !a.seeded;
-    for (long long e = (long long)blockIdx.x * 256 + tid; e < n; e += (long long)GND_NB * 256) {
+    for (long long e = (long long)blockIdx.x * 256 + tid; e < n; e += (long long)FIT_NB * 256) {
       const int gy = (int)(e / nx), gx = (int)(e - (long long)gy * nx);
       const int x = gx * a.step, y = gy * a.step;
       const float d = a.disp[(size_t)y * a.W + x];
@@ -250,7 +194,7 @@ __global__ __launch_bounds__(256) void gnd_pass_kernel(GndArgs a) {
     const float f0 = (float)sM.f[0], f1 = (float)sM.f[1], f2 = (float)sM.f[2];
     const float half = 0.5f * (float)a.gw;
     // (the trip count is the workgroup's: every lane takes part in the shuffles below)
-    for (long long e0 = (long long)blockIdx.x * 256; e0 < n; e0 += (long long)GND_NB * 256) {
+    for (long long e0 = (long long)blockIdx.x * 256; e0 < n; e0 += (long long)FIT_NB * 256) {
       const long long e = e0 + tid;
       int key = -1, hb = 0;
       if (e < n) {
@@ -308,41 +252,27 @@ __global__ __launch_bounds__(256) void gnd_pass_kernel(GndArgs a) {
     }
   }
 
-#pragma unroll
-  for (int i = 0; i < NACC; ++i) {
-    double v = acc[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) sRed[i][wave] = v;
-  }
-  __syncthreads();
-  double* row = a.partial + ((size_t)(a.k & 1) * GND_NB + blockIdx.x) * GND_NS;
-  if (tid < NACC) row[tid] = sRed[tid][0] + sRed[tid][1] + sRed[tid][2] + sRed[tid][3];
+  fit_reduce_store<NACC>(acc, sRed, a.partial + ((size_t)(a.k & 1) * FIT_NB + blockIdx.x) * GND_NS);
   if (!LAST) return;
 
   // ---- the record: the workgroup that draws the last ticket adds the last pass's rows
-  __threadfence();  // this workgroup's row, labels and grid updates, device-wide, before its ticket
-  __syncthreads();
-  if (tid == 0) sLast = atomicAdd(a.ticket, 1u) == (unsigned)(GND_NB - 1);
-  __syncthreads();
-  if (!sLast) return;
-  __threadfence();  // every other row, before they are read
-  gnd_sum_rows<3>(a.partial + (size_t)(a.k & 1) * GND_NB * GND_NS, sF);
+  if (!fit_last_workgroup(a.ticket)) return;
+  fit_sum_rows<GND_NS, 3>(a.partial + (size_t)(a.k & 1) * FIT_NB * GND_NS, sF);
   __syncthreads();
   const bool ok = sM.ok != 0 && sF[1] >= (double)a.min_valid;
   if (tid == 0) {
     double* rec = a.record;
-    for (int i = 0; i < 3; ++i) rec[i] = gnd_clean(sSt[i]);
+    for (int i = 0; i < 3; ++i) rec[i] = fit_clean(sSt[i]);
     rec[3] = ok ? 1.0 : 0.0;
     rec[4] = sF[0];
     rec[5] = sF[1];
-    rec[6] = sF[1] > 0.0 ? gnd_clean(sqrt(sF[2] / sF[1])) : 0.0;
+    rec[6] = sF[1] > 0.0 ? fit_clean(sqrt(sF[2] / sF[1])) : 0.0;
     rec[7] = sSt[4];
-    for (int i = 0; i < 3; ++i) rec[8 + i] = gnd_clean(sM.n[i]);
-    rec[11] = gnd_clean(sM.Hc);
-    rec[12] = gnd_clean(sM.tilt);
-    for (int i = 0; i < 9; ++i) rec[13 + i] = gnd_clean(sS[i]);  // the last step's A (upper triangle) and b
-    for (int i = 0; i < 3; ++i) rec[22 + i] = gnd_clean(sM.f[i]);
+    for (int i = 0; i < 3; ++i) rec[8 + i] = fit_clean(sM.n[i]);
+    rec[11] = fit_clean(sM.Hc);
+    rec[12] = fit_clean(sM.tilt);
+    for (int i = 0; i < 9; ++i) rec[13 + i] = fit_clean(sS[i]);  // the last step's A (upper triangle) and b
+    for (int i = 0; i < 3; ++i) rec[22 + i] = fit_clean(sM.f[i]);
     for (int i = 25; i < 32; ++i) rec[i] = 0.0;
   }
   if (sM.ok != 0 && !ok) {
@@ -370,8 +300,7 @@ static inline bool gnd_grid_ok(int gh, int gw) {
 
 extern "C" long long codd_ground_scratch(int h, int w, int gh, int gw) {
   if (h <= 0 || w <= 0 || (long long)h * w >= (1LL << 31) || !gnd_grid_ok(gh, gw)) return -1;
-  // 16 bytes of slack (the call aligns the caller's pointer itself), rows + states, the ticket
-  return 16 + 8LL * (2 * GND_NB * GND_NS + 2 * GND_STATE) + 16;
+  return fit_scratch_bytes(GND_NS, GND_STATE);
 }
 
 extern "C" int codd_ground_plane(const float* disp, int H, int W, int h, int w, float fx, float fy, float cx, float cy,
@@ -398,12 +327,10 @@ extern "C" int codd_ground_plane(const float* disp, int H, int W, int h, int w, 
   if (seed && !(fabs(seed[0]) < (double)INFINITY && fabs(seed[1]) < (double)INFINITY && fabs(seed[2]) < (double)INFINITY))
     return CODD_EINVAL;
   if (scratch_bytes < codd_ground_scratch(h, w, gh, gw)) return CODD_EINVAL;
-  char* base = (char*)(((uintptr_t)scratch + 15) & ~(uintptr_t)15);
+  const FitScratch f = fit_carve(scratch, GND_NS, GND_STATE);
   GndArgs a;
   a.disp = disp;
-  a.partial = (double*)base;
-  a.state = a.partial + 2 * GND_NB * GND_NS;
-  a.ticket = (unsigned*)(a.state + 2 * GND_STATE);
+  a.partial = f.partial; a.state = f.state; a.ticket = f.ticket;
   a.record = record; a.labels = labels; a.height = height;
   a.grid_count = grid_count; a.grid_height = (int*)grid_height;
   for (int i = 0; i < 3; ++i) { a.seed[i] = seed ? seed[i] : 0.0; a.up[i] = u[i] / ul; }
@@ -421,9 +348,9 @@ extern "C" int codd_ground_plane(const float* disp, int H, int W, int h, int w, 
       const float sk = fmaxf(delta_px, ldexpf(delta0_px, -k)), sp = sk / asym;
       a.s2_neg = sk * sk;
       a.s2_pos = sp * sp;
-      gnd_pass_kernel<false><<<GND_NB, 256, 0, s>>>(a);
+      gnd_pass_kernel<false><<<FIT_NB, 256, 0, s>>>(a);
     } else {
-      gnd_pass_kernel<true><<<GND_NB, 256, 0, s>>>(a);
+      gnd_pass_kernel<true><<<FIT_NB, 256, 0, s>>>(a);
     }
     CODD_LAUNCH_CHECK();
   }

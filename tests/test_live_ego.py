@@ -201,6 +201,8 @@ def test_ego_motion_scratch_is_positive_and_monotone():
     assert sizes[0] > 0 and sizes == sorted(sizes) and len(set(sizes)) == len(sizes)
     assert lib.codd_ego_motion_scratch(54, 960) == lib.codd_ego_motion_scratch(540, 96)  # a function of h * w
     assert lib.codd_ego_motion_scratch(0, 5) < 0 and lib.codd_ego_motion_scratch(5, -1) < 0
+    for h, w in ((1, 1), (37, 53), (540, 960)):  # the layout is part of the contract: rows, states, ticket; X1 behind them
+        assert lib.codd_ego_motion_scratch(h, w) == 82208 + 12 * h * w
 
 
 def test_run_live_streams_the_ego_file(tmp_path, monkeypatch):

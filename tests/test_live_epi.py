@@ -147,6 +147,8 @@ def test_entry_rejects_bad_arguments():
     lib = _abi.load()
     assert not _abi.MISSING and lib.codd_epipolar_scratch(0, 4) == -1 and lib.codd_epipolar_scratch(4, -1) == -1
     assert lib.codd_epipolar_scratch(65536, 32768) == -1 and lib.codd_epipolar_scratch(37, 61) > 12 * 37 * 61
+    for h, w in ((1, 1), (37, 53), (540, 960)):  # the layout is part of the contract: rows, states, ticket; three planes
+        assert lib.codd_epipolar_scratch(h, w) == 65696 + 12 * h * w
     need = lib.codd_epipolar_scratch(24, 40)
     buf = np.zeros(64, np.uint8)  # host memory standing in for device pointers: never dereferenced
     p = buf.ctypes.data_as(C.c_void_p)

@@ -211,6 +211,8 @@ def test_entry_rejects_bad_arguments():
     assert scr(4, 4, 0, 3) == -1 and scr(4, 4, 3, 0) == -1 and scr(4, 4, -1, -1) == -1 and scr(4, 4, 32768, 32768) == -1
     need = scr(24, 40, 7, 5)
     assert need > 0 and scr(24, 40, 0, 0) == need and scr(46340, 46340, 0, 0) == need  # the sums only: no plane per pixel
+    for h, w in ((1, 1), (37, 53), (540, 960)):  # the layout is part of the contract: rows, states, ticket
+        assert scr(h, w, 0, 0) == 41120 and scr(h, w, 128, 128) == 41120
     buf = np.zeros(64, np.uint8)  # host memory standing in for device pointers: never dereferenced
     p = buf.ctypes.data_as(C.c_void_p)
     up = (C.c_float * 3)(0.0, -1.0, 0.0)

@@ -6,7 +6,7 @@ import pytest
 
 import parent_bits as P
 
-NAMES = ("conv_epilogue", "conv_epilogue_vec", "convb_epilogue", "load_chain", "ingest", "conv_plan")
+NAMES = ("conv_epilogue", "conv_epilogue_vec", "convb_epilogue", "load_chain", "ingest", "conv_plan", "live_fit")
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -9,7 +9,7 @@ This is how a same-bits change is fenced.  The fixture is made ONCE, with the li
 (built apart and loaded through CODD_LIB_AB), never with the library of the tree that holds it: a test
 tests/test_gpu_<name>_bits.py then holds the in-tree library to those digests, and parent_bits.assert_from_another_commit
 (tests/parent_bits.py) refuses a fixture that names the commit under test.  <name>: conv_epilogue, conv_epilogue_vec,
-convb_epilogue, load_chain, ingest, and conv_plan -- host decisions, not output bytes: no GPU, run in a checkout of the parent
+convb_epilogue, load_chain, ingest, live_fit, and conv_plan -- host decisions, not output bytes: no GPU, run in a checkout of the parent
 commit with the case module copied in; a new fence adds its case module (NAME, SOURCES, groups()), its fixture and its test.
     --stub   no GPU: enumerate the keys only (every digest "stub"); the key list must not depend on the library."""
 import argparse
