@@ -149,6 +149,9 @@ SIGNATURES = {
     "codd_ground_scratch": (_ll, [_i, _i, _i, _i]),
     "codd_ground_plane": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _f, C.POINTER(C.c_double), c_float_p, _i, _i, _f, _f, _f,
                                _i, _f, _f, _f, _f, _f, _i, _i, _p, _ll, _p, _p, _p, _p, _p, _p]),
+    "codd_objects_scratch": (_ll, [_i, _i, _i]),
+    "codd_objects": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, C.c_uint, _f, _f, _i, _f, _i, _p, _ll, _p, _p, _p, _p,
+                          _p]),
     "codd_align_depth": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, C.POINTER(AlignView), _i, _i, _i, _p, _p, _p]),
 }
 

@@ -76,6 +76,13 @@ def parse_args(argv=None):
     p.add_argument("--ground-grid", default=None, metavar="GHxGW",
                    help="--ground: also a top-down grid of GH rows (forward) x GW columns (right) on the floor")
     p.add_argument("--ground-cell", type=float, default=None, help="--ground-grid: the side of a cell (default 0.1)")
+    p.add_argument("--objects", action="store_true",
+                   help="--ground: the obstacles as objects (connected components of the obstacle pixels); also write "
+                        "<name>.objects.pred.npz: n and found [1, frames] and, padded with zeros to MAX = the session's "
+                        "max_objects, pixels [1, frames, MAX], box [1, frames, MAX, 4] (x0, y0, x1, y1), near_px [1, frames, MAX, 2], "
+                        "key [1, frames, MAX], extent [1, frames, MAX, 4] (gx_min, gx_max, gz_min, gz_max), height and "
+                        "disparity [1, frames, MAX, 2] (min, max); with --show also ids [1, frames, h, w] uint16 (the object "
+                        "number of every pixel, 65535 for none)")
     p.add_argument("--align-footprint", type=int, default=None, choices=[1, 2, 3, 4],
                    help="--align: target pixels per source pixel and axis (default: the smallest that leaves no hole lines)")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
@@ -129,6 +136,8 @@ def parse_args(argv=None):
         p.error("--ground needs --live")
     if (args.ground_height is not None or args.ground_grid is not None) and not args.ground:
         p.error("--ground-height / --ground-grid need --ground")
+    if args.objects and not args.ground:
+        p.error("--objects needs --ground")
     if args.ground_grid is not None:
         m = re.fullmatch(r"(\d+)x(\d+)", args.ground_grid)
         if not m or not int(m.group(1)) or not int(m.group(2)):
@@ -300,7 +309,9 @@ def run_live(args, model, videos):
     <name>.epi.pred.npz (per-frame coefficients, counts, rms and normal equations plus the combined coefficients; one line
     with the rms vertical disparity and the combined rotation is printed with or without --show) and, with --ground,
     <name>.ground.pred.npz (per-frame plane, ok, normal, camera height and labels, and the grids with --ground-grid; one
-    line with the frames in which a floor was found is printed with or without --show).  With --pixel-format the
+    line with the frames in which a floor was found is printed with or without --show) and, with --objects,
+    <name>.objects.pred.npz (per-frame n, found and the object tables padded to max_objects, written with or without
+    --show; the id maps with --show only).  With --pixel-format the
     frame files are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU.  With
     --calibration the frames (files or --frame-size) have the calibration's source size and every result has --net-size."""
     from PIL import Image
@@ -324,6 +335,8 @@ def run_live(args, model, videos):
         if args.ground_cell is not None:
             g["cell"] = args.ground_cell
         extra["ground"] = g
+    if getattr(args, "objects", False):
+        extra["objects"] = dict(map=bool(args.show))
     raw = getattr(args, "pixel_format", None)
     if raw:
         extra.update(pixel_format=raw, pitch=args.pitch, yuv=args.yuv or "bt601")
@@ -363,11 +376,14 @@ def run_live(args, model, videos):
             if align_to:
                 aligned = _NpzStream(osp.join(args.show_dir, name + ".aligned.pred.npz"), "depth",
                                      (1, nf) + s.align_target.camera.size, np.float32)
-        n, epis, grounds = 0, [], []
+        n, epis, grounds, objs = 0, [], [], []
         try:
             frames = iter_raw_frames(lefts, rights, raw, src, args.pitch) if raw else iter_frames(lefts, rights)
             for res in live_results(s, frames):
                 n += 1
+                if "objects" in extra:
+                    res, ob = res[:-1], res[-1]  # (a Ground precedes it: still a tuple)
+                    objs.append(ob)
                 if "ground" in extra:
                     res, g = res[:-1] if (args.motion or args.ego or args.confidence or align_to
                                           or "epipolar" in extra) else res[0], res[-1]
@@ -436,6 +452,24 @@ def run_live(args, model, videos):
             print(f"{name}: ground: floor found in {len(good)} of {len(grounds)} frames"
                   + (f"; camera height {np.mean(hs):.3f} (min {min(hs):.3f}, max {max(hs):.3f}), tilt against up "
                      f"{np.mean(ts):.1f} degrees" if good else ""))
+        if "objects" in extra:
+            m = s.objects["max_objects"]
+
+            def table(field, tail, dt):
+                t = np.zeros((1, len(objs), m) + tail, dt)
+                for i, ob in enumerate(objs):
+                    t[0, i, :ob.n] = getattr(ob, field)
+                return t
+
+            os.makedirs(args.show_dir, exist_ok=True)
+            np.savez(osp.join(args.show_dir, name + ".objects.pred.npz"), n=np.array([[ob.n for ob in objs]], np.int32),
+                     found=np.array([[ob.found for ob in objs]], np.int32), pixels=table("pixels", (), np.int32),
+                     box=table("box", (4,), np.int32), near_px=table("near_px", (2,), np.int32), key=table("key", (), np.int32),
+                     extent=table("extent", (4,), np.float32), height=table("height", (2,), np.float32),
+                     disparity=table("disparity", (2,), np.float32),
+                     **(dict(ids=np.array([[ob.ids for ob in objs]])) if args.show else {}))
+            print(f"{name}: objects: {sum(ob.n for ob in objs)} in {len(objs)} frames"
+                  + (f", most in one frame {max(ob.n for ob in objs)}" if objs else ""))
         print(f"{name}: {n} frames")
     for s in sessions.values():
         s.close()

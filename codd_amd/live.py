@@ -51,6 +51,12 @@ With ``ground=`` the session finds the floor: ``codd_ground_plane`` runs after t
 disparity, fits one plane robustly in disparity space and returns per pixel the height above it and a label (floor,
 obstacle, overhead, below), plus, on request, a top-down grid of the floor and obstacle pixels a planner can read.  It
 needs no motion stage and no ``calibration=``.
+
+With ``objects=`` (which needs ``ground=``) the session says what the obstacles are: ``codd_objects`` runs right after
+``codd_ground_plane`` on its device labels and record, joins the labelled pixels into connected components along
+4-neighbour edges whose disparity step is small, and returns a short table -- per object the pixel count, the image
+box, the nearest pixel and the extents in the ground grid's frame, in height and in disparity -- and, on request, the
+per-pixel object number.
 """
 from collections import deque, namedtuple
 
@@ -73,6 +79,10 @@ EPI_DEFAULTS = dict(range_px=2, step=2, tau=24.0, min_curv=0.5, iters=4, delta_p
 GROUND_DEFAULTS = dict(step=2, iters=8, delta_px=0.25, delta0_px=4.0, asym=4.0, min_valid=256, max_tilt_deg=45.0, tol_px=0.5,
                        ground_tol=0.05, clearance=2.0, height=None, pitch_deg=0.0, up=(0, -1, 0), map=False, grid=None,
                        cell=0.1)
+OBJECT_DEFAULTS = dict(select=("obstacle",), gap_px=1.0, gap_rel=0.05, min_pixels=64, min_height=0.15, max_objects=256,
+                       map=False)
+OBJECT_LABELS = dict(floor=ops.GROUND_FLOOR, obstacle=ops.GROUND_OBSTACLE, overhead=ops.GROUND_OVERHEAD,
+                     below=ops.GROUND_BELOW)  # the names ``select`` takes
 
 # One frame's ego-motion, caller-owned: pose fp32 [7] = (t, q_xyzw) of G, the rigid motion that maps static points from
 # the previous camera frame to the current one (t in the unit of calib; the camera itself moved by G^-1); ok (False: the
@@ -136,6 +146,26 @@ def ground_from_record(rec, labels, height=None, grid_count=None, grid_height=No
     rec = np.asarray(rec, np.float64)
     return Ground(rec[0:3].copy(), bool(rec[3] != 0), rec[8:11].copy(), float(rec[11]), float(rec[12]), rec[22:25].copy(),
                   int(rec[4]), int(rec[5]), float(rec[6]), int(rec[7]), labels, height, grid_count, grid_height)
+
+
+# One frame's obstacle objects, caller-owned: n objects (at most max_objects), in raster order of their first pixel; found
+# components that passed min_pixels and min_height (> n: the list was truncated); components and foreground pixels in
+# all; pixels int32 [n]; box int32 [n,4] (x0, y0, x1, y1, inclusive); near_px int32 [n,2] (x, y) of the pixel with the
+# largest disparity; key int32 [n], the raster index y * w + x of the object's first pixel; extent fp32 [n,4] (gx_min, gx_max,
+# gz_min, gz_max) in the frame of Ground.grid_count (gx to the right, gz forward, the camera above the origin); height
+# fp32 [n,2] (lowest, highest pixel above the floor); disparity fp32 [n,2] (smallest, largest: depth = calib / disparity);
+# ids uint16 [h,w] (None unless objects=dict(map=True)): the object number of every pixel, 0xFFFF for none.
+Objects = namedtuple("Objects", "n found components foreground pixels box near_px key extent height disparity ids")
+
+
+def objects_from_buffers(count, obj_i, obj_f, ids=None):
+    """count int32 [4], obj_i int32 [max_objects,8] and obj_f fp32 [max_objects,8] of codd_objects (include/codd_hip.h) and
+    its id map -> ``Objects``, the tables sliced to the n objects (copies: the buffers may be reused)."""
+    count, obj_i, obj_f = np.asarray(count, np.int32), np.asarray(obj_i, np.int32), np.asarray(obj_f, np.float32)
+    n = int(count[0])
+    return Objects(n, int(count[1]), int(count[2]), int(count[3]), obj_i[:n, 0].copy(), obj_i[:n, 1:5].copy(),
+                   obj_i[:n, 5:7].copy(), obj_i[:n, 7].copy(), obj_f[:n, 0:4].copy(), obj_f[:n, 4:6].copy(),
+                   obj_f[:n, 6:8].copy(), ids)
 
 
 def _unit_up(up, pitch_deg=0.0):
@@ -360,6 +390,53 @@ def _check_ground(ground):
     return p
 
 
+def _check_objects(objects, ground=True):
+    """False / None -> None; True -> the defaults; a dict overrides them.  ValueError otherwise, and for ``objects``
+    without ``ground`` (no device call)."""
+    if objects is None or objects is False:
+        return None
+    if not (objects is True or isinstance(objects, dict)):
+        raise ValueError(f"objects: False, True or a dict of {tuple(OBJECT_DEFAULTS)} expected, got {objects!r}")
+    if ground is None or ground is False:
+        raise ValueError("objects: needs ground= (the components are those of the ground stage's labels)")
+    if objects is True:
+        return dict(OBJECT_DEFAULTS)
+    unknown = set(objects) - set(OBJECT_DEFAULTS)
+    if unknown:
+        raise ValueError(f"objects: unknown keys {sorted(unknown)}; known: {tuple(OBJECT_DEFAULTS)}")
+    p = dict(OBJECT_DEFAULTS, **objects)
+    is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+    sel = p["select"]
+    if isinstance(sel, str):
+        sel = (sel,)
+    if not (isinstance(sel, (tuple, list)) and len(sel) > 0 and all(isinstance(v, str) and v in OBJECT_LABELS for v in sel)):
+        raise ValueError(f"objects: select: one or more of {tuple(OBJECT_LABELS)} expected, got {p['select']!r}")
+    p["select"] = tuple(sel)
+    if not (is_int(p["max_objects"]) and 1 <= p["max_objects"] <= ops.OBJECT_MAX):
+        raise ValueError(f"objects: an integer max_objects in [1, {ops.OBJECT_MAX}] expected, got {p['max_objects']!r}")
+    if not (is_int(p["min_pixels"]) and p["min_pixels"] >= 1):
+        raise ValueError(f"objects: an integer min_pixels >= 1 expected, got {p['min_pixels']!r}")
+    for k in ("gap_px", "gap_rel", "min_height"):
+        try:
+            p[k] = float(p[k])
+        except (TypeError, ValueError):
+            raise ValueError(f"objects: a number expected for {k}, got {p[k]!r}") from None
+        if not np.isfinite(p[k]):
+            raise ValueError(f"objects: a finite {k} expected, got {p[k]!r}")
+    if not p["gap_px"] > 0:
+        raise ValueError(f"objects: positive gap_px expected, got {p['gap_px']!r}")
+    if not p["gap_rel"] >= 0:
+        raise ValueError(f"objects: gap_rel >= 0 expected, got {p['gap_rel']!r}")
+    if not isinstance(p["map"], bool):
+        raise ValueError(f"objects: map True or False expected, got {p['map']!r}")
+    return p
+
+
+def select_mask(names):
+    """The ``select`` bit set of codd_objects for label names of ``OBJECT_LABELS``."""
+    return sum({1 << OBJECT_LABELS[v] for v in names})
+
+
 def _check_align(align, align_to):
     """None -> the defaults; a dict overrides them.  ValueError otherwise, and for ``align`` without ``align_to``."""
     if align is None:
@@ -490,7 +567,7 @@ class LiveSession:
 
     ``egomotion`` (False, True, or a dict overriding ``iters``, ``delta_px``, ``tau_px``, ``min_valid``): ``pop`` and
     ``step`` also return an ``Ego`` (or None for a frame without a field).  The tuple order is fixed:
-    ``result[, motion][, ego][, confidence][, aligned][, epipolar][, ground]``, each part present iff requested.
+    ``result[, motion][, ego][, confidence][, aligned][, epipolar][, ground][, objects]``, each part present iff requested.
 
     ``confidence`` (False, True, or a dict overriding ``occ_px`` (1.0 pixel) and ``tau`` (24.0 grey levels)): ``pop`` and
     ``step`` also return a ``Confidence(flags, residual)`` on the CURRENT frame's grid, for every frame (never None).  It
@@ -542,12 +619,23 @@ class LiveSession:
     A pixel within ``tol_px`` of disparity or ``ground_tol`` of height of the plane is floor; above it, up to
     ``clearance``, an obstacle.  Heights are in the unit of ``calib`` / fx.  It needs no motion stage and no
     ``calibration=``; it uses the session's ``intrinsics`` and ``calib``.  Defined in include/codd_hip.h (codd_ground_plane).
+
+    ``objects`` (False, True, or a dict overriding ``OBJECT_DEFAULTS``; needs ``ground``, ValueError without): ``pop`` and
+    ``step`` also return an ``Objects``, for every frame (never None), last in the tuple: the connected components of the
+    pixels whose label is one of ``select`` (names of ``OBJECT_LABELS``; by default the obstacles), two 4-neighbours being
+    joined when their disparities differ by at most ``max(gap_px, gap_rel * the smaller one)``.  A component with at least
+    ``min_pixels`` pixels whose top is at least ``min_height`` above the floor is an object; objects are numbered in
+    raster order of their first pixel and the first ``max_objects`` (1 .. 4096) are returned (``found`` > ``n``: there were
+    more).  Per object: ``pixels``, the image ``box``, the nearest pixel ``near_px``, the ``extent`` in the ground grid's
+    frame, the ``height`` range above the floor and the ``disparity`` range; ``map`` True also returns ``ids`` uint16
+    [h,w], the object number of every pixel (0xFFFF: none).  A frame without a floor has no objects.  Defined in
+    include/codd_hip.h (codd_objects).
     """
 
     def __init__(self, estimator, shape, intrinsics=None, calib=None, output="depth",
                  bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False,
                  pixel_format="rgb8", yuv="bt601", pitch=None, calibration=None, zoom=1.0, align_to=None, align=None,
-                 epipolar=False, ground=False):
+                 epipolar=False, ground=False, objects=False):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
@@ -560,6 +648,7 @@ class LiveSession:
         self.conf = _check_conf(confidence)
         self.epi = _check_epi(epipolar)
         self.ground = _check_ground(ground)
+        self.objects = _check_objects(objects, self.ground)
         h, w = int(shape[0]), int(shape[1])
         if h <= 0 or w <= 0:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
@@ -597,6 +686,8 @@ class LiveSession:
             self._ground_seed = None if g["height"] is None else ground_seed(g["height"], self._epi_K, calib, g["up"],
                                                                              g["pitch_deg"])
             self._ground_par = {k: g[k] for k in ops.GROUND_PARAMS}
+        if self.objects is not None:
+            self._objects_par = dict({k: self.objects[k] for k in ops.OBJECT_PARAMS}, select=select_mask(self.objects["select"]))
         self.src_shape = (h, w) if self.rect is None else self.rect.size  # the size of a frame as the camera hands it out
         # (rows, row_bytes, pitch, nbytes) of a source frame; ValueError if invalid
         self._layout = frame_layout(pixel_format, self.src_shape[0], self.src_shape[1], pitch)
@@ -687,6 +778,16 @@ class LiveSession:
                 self._h_ground = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_ground]
                                   for _ in range(DEPTH)]
                 self._ground_scratch = torch.empty(ops.ground_scratch(h, w, grid), dtype=torch.uint8, device=dev)
+            if self.objects is not None:
+                m = self.objects["max_objects"]
+                self._d_objects = [torch.zeros(4, dtype=torch.int32, device=dev),
+                                   torch.zeros(m, 8, dtype=torch.int32, device=dev),
+                                   torch.zeros(m, 8, dtype=torch.float32, device=dev)]
+                if self.objects["map"]:
+                    self._d_objects.append(torch.empty(h, w, dtype=torch.uint16, device=dev))
+                self._h_objects = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_objects]
+                                   for _ in range(DEPTH)]
+                self._objects_scratch = torch.empty(ops.objects_scratch(h, w, m), dtype=torch.uint8, device=dev)
             self._s_up, self._s_down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             ev = lambda: [torch.cuda.Event() for _ in range(DEPTH)]  # noqa: E731
             self._e_up, self._e_ingest, self._e_export, self._e_down = ev(), ev(), ev(), ev()
@@ -761,6 +862,10 @@ class LiveSession:
                 ops.ground_plane(disp, self._epi_K, self.calib, self.shape, *self._ground_bufs(self._d_ground),
                                  scratch=self._ground_scratch, seed=self._ground_seed, up=self._ground_up,
                                  **self._ground_par)
+            if self.objects is not None:
+                ops.objects(disp, self._epi_K, self.calib, self.shape, self._d_ground[1], self._d_ground[0],
+                            *self._d_objects[:3], ids=self._d_objects[3] if self.objects["map"] else None,
+                            scratch=self._objects_scratch, **self._objects_par)
             Ts = None
             if self.motion is not None or self.ego is not None:
                 Ts = self.runner.last.get("Ts")  # None: the frame has no field (first of a sequence) -- roll only
@@ -797,6 +902,9 @@ class LiveSession:
                 if self.ground is not None:
                     for host, dev_buf in zip(self._h_ground[k], self._d_ground):
                         host.copy_(dev_buf, non_blocking=True)
+                if self.objects is not None:
+                    for host, dev_buf in zip(self._h_objects[k], self._d_objects):
+                        host.copy_(dev_buf, non_blocking=True)
                 self._e_down[k].record(self._s_down)
         self._inflight.append(k)
         self._pushed += 1
@@ -821,6 +929,9 @@ class LiveSession:
             out.append(epipolar_from_record(got[0], got[1] if self.epi["map"] else None))
         if self.ground is not None:
             out.append(ground_from_record(*self._ground_bufs([t.numpy().copy() for t in self._h_ground[k]])))
+        if self.objects is not None:
+            got = [t.numpy() for t in self._h_objects[k]]  # (objects_from_buffers copies what it keeps)
+            out.append(objects_from_buffers(got[0], got[1], got[2], got[3].copy() if self.objects["map"] else None))
         return out[0] if len(out) == 1 else tuple(out)
 
     def _ground_bufs(self, bufs):
@@ -842,7 +953,7 @@ class LiveSession:
         """The oldest frame's result: numpy [h,w] (fp32, or uint16 for ``disp_u16``), owned by the caller; with a
         ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None; with ``egomotion``, an ``Ego`` or None
         follows; with ``confidence``, a ``Confidence``; with ``align_to``, an ``Aligned``; with ``epipolar``, an
-        ``Epipolar``; with ``ground``, a ``Ground`` comes last."""
+        ``Epipolar``; with ``ground``, a ``Ground``; with ``objects``, an ``Objects`` comes last."""
         if self._ready:
             return self._ready.popleft()
         if not self._inflight:
@@ -873,7 +984,8 @@ class LiveSession:
             self._s_down.synchronize()
             for name in ("_h_in", "_d_in", "_scratch", "_maps", "_d_out", "_h_out", "_depth_prev", "_d_mot", "_h_mot",
                          "_d_ego", "_h_ego", "_ego_scratch", "_d_conf", "_h_conf", "_d_align", "_h_align",
-                         "_d_epi", "_h_epi", "_epi_scratch", "_d_ground", "_h_ground", "_ground_scratch"):
+                         "_d_epi", "_h_epi", "_epi_scratch", "_d_ground", "_h_ground", "_ground_scratch",
+                         "_d_objects", "_h_objects", "_objects_scratch"):
                 setattr(self, name, None)
             self._open_done = False
         self._inflight.clear()

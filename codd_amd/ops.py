@@ -2143,6 +2143,63 @@ def ground_plane(disp, K, calib, crop, record, labels, height=None, grid_count=N
     return record
 
 
+OBJECT_PARAMS = dict(select=1 << GROUND_OBSTACLE, gap_px=1.0, gap_rel=0.05, min_pixels=64, min_height=0.15, max_objects=256)
+OBJECT_MAX = 4096  # the largest max_objects (include/codd_hip.h)
+
+
+def objects_scratch(h, w, max_objects=OBJECT_PARAMS["max_objects"]):
+    """Bytes of scratch ``objects`` needs for an h x w crop (codd_objects_scratch)."""
+    n = int(_abi.load().codd_objects_scratch(int(h), int(w), int(max_objects)))
+    if n <= 0:
+        raise ValueError(f"objects_scratch: positive (h, w) with h w < 2^31 and max_objects in [1, {OBJECT_MAX}] expected, "
+                         f"got {(h, w)}, {max_objects}")
+    return n
+
+
+def objects(disp, K, calib, crop, labels, ground_record, count, obj_i, obj_f, ids=None, scratch=None, **par):
+    """What are the obstacles?  The connected components (4-neighbours whose disparities differ by at most
+    max(gap_px, gap_rel * the smaller one)) of the pixels of the ``crop`` (h, w) of the padded disparity ``disp`` [H,W] (or
+    [1,1,H,W]) whose label in ``labels`` uint8 [h,w] is in the bit set ``select``, and one table row for each of the first
+    ``max_objects`` components, in raster order of their first pixel, with at least ``min_pixels`` pixels and a top at
+    least ``min_height`` above the floor (include/codd_hip.h, codd_objects).  ``labels`` and ``ground_record`` (float64
+    [32]) are the device tensors ``ground_plane`` wrote, ``K`` and ``calib`` the ones it took.  Outputs are caller-owned
+    device tensors: ``count`` int32 [4] (objects, passing components, components, foreground pixels); ``obj_i`` int32
+    [max_objects,8] (pixels, x0, y0, x1, y1, near_x, near_y, key); ``obj_f`` fp32 [max_objects,8] (gx_min, gx_max, gz_min,
+    gz_max, hgt_min, hgt_max, d_min, d_max), rows past the objects zero; ``ids`` uint16 [h,w] or None (the object number
+    of every pixel, 0xFFFF for none).  ``par`` overrides ``OBJECT_PARAMS`` (``max_objects`` is the tables' row count).
+    ``scratch``: a uint8 tensor of ``objects_scratch`` bytes; allocated here when None.  7 launches on the current
+    stream (6 without ``ids``), no host synchronisation."""
+    lib = _abi.load()
+    _require_gpu(disp)
+    unknown = set(par) - set(OBJECT_PARAMS)
+    if unknown:
+        raise TypeError(f"objects: unknown parameters {sorted(unknown)}; known: {tuple(OBJECT_PARAMS)}")
+    H, W = disp.shape[-2:]
+    h, w = int(crop[0]), int(crop[1])
+    assert obj_i.dim() == 2, "obj_i: [max_objects,8] expected"
+    p = dict(OBJECT_PARAMS, max_objects=int(obj_i.shape[0]))
+    p.update(par)
+    m = int(p["max_objects"])
+    assert disp.dtype == torch.float32 and disp.is_cuda and disp.is_contiguous() and disp.numel() == H * W
+    assert labels.dtype == torch.uint8 and labels.is_cuda and labels.is_contiguous() and tuple(labels.shape) == (h, w)
+    assert ground_record.dtype == torch.float64 and ground_record.is_cuda and ground_record.is_contiguous()
+    assert ground_record.numel() == 32
+    assert count.dtype == torch.int32 and count.is_cuda and count.is_contiguous() and count.numel() == 4
+    assert obj_i.dtype == torch.int32 and obj_i.is_cuda and obj_i.is_contiguous() and tuple(obj_i.shape) == (m, 8)
+    assert obj_f.dtype == torch.float32 and obj_f.is_cuda and obj_f.is_contiguous() and tuple(obj_f.shape) == (m, 8)
+    if ids is not None:
+        assert ids.dtype == torch.uint16 and ids.is_cuda and ids.is_contiguous() and tuple(ids.shape) == (h, w)
+    if scratch is None:
+        scratch = torch.empty(objects_scratch(h, w, m), dtype=torch.uint8, device=disp.device)
+    assert scratch.dtype == torch.uint8 and scratch.is_cuda and scratch.is_contiguous()
+    _abi.check(lib.codd_objects(disp.data_ptr(), H, W, h, w, *[float(v) for v in K], float(calib), labels.data_ptr(),
+                                ground_record.data_ptr(), int(p["select"]), float(p["gap_px"]), float(p["gap_rel"]),
+                                int(p["min_pixels"]), float(p["min_height"]), m, scratch.data_ptr(), scratch.numel(),
+                                count.data_ptr(), obj_i.data_ptr(), obj_f.data_ptr(),
+                                None if ids is None else ids.data_ptr(), _stream()), "objects")
+    return count
+
+
 ALIGN_MAX_FOOTPRINT = 4  # CODD_ALIGN_MAX_FOOTPRINT of include/codd_hip.h
 
 

@@ -977,6 +977,59 @@ int codd_ground_plane(const float* disp, int H, int W, int h, int w, float fx, f
                       int gw, void* scratch, long long scratch_bytes, double* record, unsigned char* labels, float* height,
                       int* grid_count, float* grid_height, void* stream);
 
+/* Live-session obstacle objects (codd_amd/live.py, objects=): the connected components of the pixels codd_ground_plane
+ * labelled, and per component a row of a fixed-size table.  The reference has no such output; this replaces downloading
+ * the label map and the disparity every frame and a connected-components pass on the host.  7 launches (6 with ids NULL;
+ * one fewer when the crop lies inside one 16 x 64 tile: the shape decides, never the data), no allocation, no host
+ * synchronisation, no loop on the host, integer atomics only: equal inputs give equal bytes.
+ * disp [H,W]: the padded disparity, read inside [0,h) x [0,w) only; K = (fx, fy, cx, cy), calib as codd_ground_plane took
+ * them.  labels [h,w]: the bytes codd_ground_plane wrote.  ground_record: the DEVICE pointer to the 32 doubles it wrote,
+ * read on the device: c = [0:3], ok = [3], n = [8:11], Hc = [11], f = [22:25].
+ * Every operation below is one fp32 operation rounded on its own (no fused multiply-add; division correctly rounded)
+ * unless it says fp64; x, y are the pixel's integer coordinates as floats.
+ *   foreground  labels[y,x] < 32 && ((select >> labels[y,x]) & 1) && d = disp[y,x] finite and > 0.  select is a bit set
+ *               over the label values (1u << CODD_GROUND_OBSTACLE: the obstacles).
+ *   edges       4-connectivity.  Neighbours a, b are joined iff both are foreground and
+ *               fabsf(da - db) <= fmaxf(gap_px, gap_rel * fminf(da, db)).
+ *   components  the connected components of that graph; a component's KEY is the smallest raster index y * w + x of its
+ *               pixels: a function of the input alone, whatever order the merges arrive in.
+ *   per pixel   p0 = x - cx;  p1 = y - cy;  e = d - ((c0 * p0 + c1 * p1) + c2);  hgt = ((float)Hc * e) / d  (the bits of
+ *               codd_ground_plane's height);  Z = calib / d;  X0 = Z * (p0 / fx);  X1 = Z * (p1 / fy);  gx = (r0 * X0 + r1 *
+ *               X1) + r2 * Z;  gz = (f0 * X0 + f1 * X1) + f2 * Z  (the ground grid's frame: gx to the right, gz forward, the
+ *               camera above the origin) with c, Hc, f, r rounded to fp32;  r = f x n in fp64 from the record's f and n,
+ *               r0 = f1 n2 - f2 n1, r1 = f2 n0 - f0 n2, r2 = f0 n1 - f1 n0, each product and each difference rounded on its
+ *               own, then rounded to fp32.  codd_ground_plane forms its r by the same expressions from the same doubles but
+ *               does not forbid the compiler a fused multiply-subtract there, so its fp64 r may differ in the last bit
+ *               and, where that bit decides the rounding, its fp32 r by one ulp: the two frames agree to one fp32 ulp of
+ *               r, not bit for bit.  hgt involves no r: it has the bits of codd_ground_plane's height map.
+ *   statistics  per component: pixels (the count); the inclusive box x0, y0, x1, y1; the NEAREST pixel: the largest d,
+ *               ties to the smallest raster index (one 64-bit maximum over (bits(d) << 32) | ~index); the minimum and
+ *               the maximum of d, hgt, gx and gz, each taken over the order-preserving integer image of the float
+ *               (o(v) = ~bits(v) with the sign bit set, bits(v) | 0x80000000 without, compared unsigned): -0 lies below
+ *               +0, and a NaN -- possible only where the plane's terms overflow -- orders by its bits (above +inf
+ *               with a clear sign bit, below -inf with a set one).
+ *   selection   a component PASSES iff pixels >= min_pixels && hgt_max >= min_height (false for a NaN).  Passing
+ *               components are numbered in ascending key order; the first max_objects (1 .. 4096) of them are the
+ *               objects 0 .. n - 1.
+ *   outputs     caller-owned device buffers.  count int32 [4]: n, the number of passing components (> n: the list was
+ *               truncated), the number of components, the number of foreground pixels.  obj_i int32 [max_objects,8]:
+ *               (pixels, x0, y0, x1, y1, near_x, near_y, key).  obj_f fp32 [max_objects,8]: (gx_min, gx_max, gz_min,
+ *               gz_max, hgt_min, hgt_max, d_min, d_max).  Rows >= n of both tables are zero: the entry clears them on
+ *               every call.  ids uint16 [h,w], 2-byte aligned, may be NULL: the object number of every pixel, 0xFFFF
+ *               where the pixel is not foreground or its component did not become an object.  With ok = 0 in the
+ *               record (no floor) nothing is foreground whatever labels holds: count = 0, zero tables, every id 0xFFFF.
+ * scratch: codd_objects_scratch(h, w, max_objects) bytes (-1 for a non-positive h or w, h w >= 2^31 or max_objects outside
+ * [1, 4096]), contents irrelevant, any alignment: the chunk counts of the numbering, the parent array (int32 per pixel) and
+ * the per-root statistics (16 int32 per pixel, touched at the roots only).
+ * CODD_EINVAL, before any launch: disp, labels, ground_record, scratch, count, obj_i or obj_f NULL; a non-positive size,
+ * h > H, w > W or h w >= 2^31; max_objects outside [1, 4096]; select 0; fx, fy, calib or gap_px not finite and > 0; cx or
+ * cy not finite; gap_rel negative or NaN; min_pixels < 1; min_height NaN; scratch_bytes below the size function's answer. */
+long long codd_objects_scratch(int h, int w, int max_objects);
+int codd_objects(const float* disp, int H, int W, int h, int w, float fx, float fy, float cx, float cy, float calib,
+                 const unsigned char* labels, const double* ground_record, unsigned select, float gap_px, float gap_rel,
+                 int min_pixels, float min_height, int max_objects, void* scratch, long long scratch_bytes, int* count,
+                 int* obj_i, float* obj_f, unsigned short* ids, void* stream);
+
 /* Ablation plug-ins.  codd_fusion_select: mode 0 = KalmanFusion (model/fusion/others.py:124-153; constant
  * gain K = Q/(Q+R), the reference never updates P), mode 1 = GTFusion (:54-86; gt [B,1,hg,wg], zero-padded).
  * cur, warp, out: [B,1,H,W]. */
