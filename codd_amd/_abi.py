@@ -152,6 +152,10 @@ SIGNATURES = {
     "codd_objects_scratch": (_ll, [_i, _i, _i]),
     "codd_objects": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, C.c_uint, _f, _f, _i, _f, _i, _p, _ll, _p, _p, _p, _p,
                           _p]),
+    "codd_track_state_bytes": (_ll, [_i, _i, _i]),
+    "codd_track_scratch": (_ll, [_i, _i, _i]),
+    "codd_track_objects": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _p, _i, _i, _i, _p, _ll, _p, _ll, _p, _p,
+                                _p, _p]),
     "codd_align_depth": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, C.POINTER(AlignView), _i, _i, _i, _p, _p, _p]),
 }
 

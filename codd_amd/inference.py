@@ -83,6 +83,12 @@ def parse_args(argv=None):
                         "key [1, frames, MAX], extent [1, frames, MAX, 4] (gx_min, gx_max, gz_min, gz_max), height and "
                         "disparity [1, frames, MAX, 2] (min, max); with --show also ids [1, frames, h, w] uint16 (the object "
                         "number of every pixel, 65535 for none)")
+    p.add_argument("--tracks", action="store_true",
+                   help="--objects, with a model that has a motion stage: persistent track ids and the motion of every "
+                        "object; also write <name>.tracks.pred.npz: n, continued, started and ended [1, frames] and, padded "
+                        "with zeros to MAX = the session's max_objects, track, age, prev, votes, pixels, moving and "
+                        "own_pixels [1, frames, MAX] and motion and own [1, frames, MAX, 3] (row k belongs to object k of "
+                        "<name>.objects.pred.npz; NaN: a started track, own also without --ego)")
     p.add_argument("--align-footprint", type=int, default=None, choices=[1, 2, 3, 4],
                    help="--align: target pixels per source pixel and axis (default: the smallest that leaves no hole lines)")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
@@ -138,6 +144,8 @@ def parse_args(argv=None):
         p.error("--ground-height / --ground-grid need --ground")
     if args.objects and not args.ground:
         p.error("--objects needs --ground")
+    if args.tracks and not args.objects:
+        p.error("--tracks needs --objects")
     if args.ground_grid is not None:
         m = re.fullmatch(r"(\d+)x(\d+)", args.ground_grid)
         if not m or not int(m.group(1)) or not int(m.group(2)):
@@ -311,7 +319,8 @@ def run_live(args, model, videos):
     <name>.ground.pred.npz (per-frame plane, ok, normal, camera height and labels, and the grids with --ground-grid; one
     line with the frames in which a floor was found is printed with or without --show) and, with --objects,
     <name>.objects.pred.npz (per-frame n, found and the object tables padded to max_objects, written with or without
-    --show; the id maps with --show only).  With --pixel-format the
+    --show; the id maps with --show only) and, with --tracks, <name>.tracks.pred.npz (per-frame n, continued, started, ended
+    and the track tables padded to max_objects, written with or without --show).  With --pixel-format the
     frame files are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU.  With
     --calibration the frames (files or --frame-size) have the calibration's source size and every result has --net-size."""
     from PIL import Image
@@ -337,6 +346,8 @@ def run_live(args, model, videos):
         extra["ground"] = g
     if getattr(args, "objects", False):
         extra["objects"] = dict(map=bool(args.show))
+    if getattr(args, "tracks", False):
+        extra["tracks"] = True
     raw = getattr(args, "pixel_format", None)
     if raw:
         extra.update(pixel_format=raw, pitch=args.pitch, yuv=args.yuv or "bt601")
@@ -376,11 +387,14 @@ def run_live(args, model, videos):
             if align_to:
                 aligned = _NpzStream(osp.join(args.show_dir, name + ".aligned.pred.npz"), "depth",
                                      (1, nf) + s.align_target.camera.size, np.float32)
-        n, epis, grounds, objs = 0, [], [], []
+        n, epis, grounds, objs, trks = 0, [], [], [], []
         try:
             frames = iter_raw_frames(lefts, rights, raw, src, args.pitch) if raw else iter_frames(lefts, rights)
             for res in live_results(s, frames):
                 n += 1
+                if "tracks" in extra:
+                    res, tr = res[:-1], res[-1]  # (a Ground and an Objects precede it: still a tuple)
+                    trks.append(tr)
                 if "objects" in extra:
                     res, ob = res[:-1], res[-1]  # (a Ground precedes it: still a tuple)
                     objs.append(ob)
@@ -470,6 +484,23 @@ def run_live(args, model, videos):
                      **(dict(ids=np.array([[ob.ids for ob in objs]])) if args.show else {}))
             print(f"{name}: objects: {sum(ob.n for ob in objs)} in {len(objs)} frames"
                   + (f", most in one frame {max(ob.n for ob in objs)}" if objs else ""))
+        if "tracks" in extra:
+            m = s.objects["max_objects"]
+
+            def padded(field, tail, dt):
+                t = np.zeros((1, len(trks), m) + tail, dt)
+                for i, tr in enumerate(trks):
+                    t[0, i, :tr.n] = getattr(tr, field)
+                return t
+
+            os.makedirs(args.show_dir, exist_ok=True)
+            np.savez(osp.join(args.show_dir, name + ".tracks.pred.npz"),
+                     **{k: np.array([[getattr(tr, k) for tr in trks]], np.int32) for k in ("n", "continued", "started", "ended")},
+                     **{k: padded(k, (), np.int32) for k in ("track", "age", "prev", "votes", "pixels", "moving", "own_pixels")},
+                     motion=padded("motion", (3,), np.float32), own=padded("own", (3,), np.float32))
+            print(f"{name}: tracks: {sum(tr.started for tr in trks)} started, {sum(tr.continued for tr in trks)} continued, "
+                  f"{sum(tr.ended for tr in trks)} ended in {len(trks)} frames"
+                  + (f", oldest {max((int(tr.age.max()) for tr in trks if tr.n), default=0)} frames" if trks else ""))
         print(f"{name}: {n} frames")
     for s in sessions.values():
         s.close()

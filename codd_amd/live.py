@@ -57,6 +57,12 @@ With ``objects=`` (which needs ``ground=``) the session says what the obstacles 
 4-neighbour edges whose disparity step is small, and returns a short table -- per object the pixel count, the image
 box, the nearest pixel and the extents in the ground grid's frame, in height and in disparity -- and, on request, the
 per-pixel object number.
+
+With ``tracks=`` (which needs ``objects=`` and an estimator with a motion stage) the session says which object is which
+across frames and how each one moves: ``codd_track_objects`` runs after ``codd_ego_motion`` and before
+``codd_export_motion`` rolls the previous depth map, carries every pixel of the previous frame's objects along the SE3
+field onto this frame's id map, lets it vote, and keeps a track id where the best matches are mutual; per object it
+returns the mean 3-D displacement of its pixels and, with ``egomotion=``, what is left of it after the camera's own motion.
 """
 from collections import deque, namedtuple
 
@@ -81,6 +87,7 @@ GROUND_DEFAULTS = dict(step=2, iters=8, delta_px=0.25, delta0_px=4.0, asym=4.0, 
                        cell=0.1)
 OBJECT_DEFAULTS = dict(select=("obstacle",), gap_px=1.0, gap_rel=0.05, min_pixels=64, min_height=0.15, max_objects=256,
                        map=False)
+TRACK_DEFAULTS = dict(min_votes=16)
 OBJECT_LABELS = dict(floor=ops.GROUND_FLOOR, obstacle=ops.GROUND_OBSTACLE, overhead=ops.GROUND_OVERHEAD,
                      below=ops.GROUND_BELOW)  # the names ``select`` takes
 
@@ -166,6 +173,27 @@ def objects_from_buffers(count, obj_i, obj_f, ids=None):
     return Objects(n, int(count[1]), int(count[2]), int(count[3]), obj_i[:n, 0].copy(), obj_i[:n, 1:5].copy(),
                    obj_i[:n, 5:7].copy(), obj_i[:n, 7].copy(), obj_f[:n, 0:4].copy(), obj_f[:n, 4:6].copy(),
                    obj_f[:n, 6:8].copy(), ids)
+
+
+# One frame's object tracks, caller-owned, row k belonging to object k of the frame's ``Objects``: n objects; continued of
+# them carry on a track of the previous frame, started begin one, and ended tracks of the previous frame found no
+# successor; track int32 [n], the persistent id (from 1; never reused within 2^31 ids); age int32 [n], the frames the track
+# has lived (1: started here); prev int32 [n], the object's number in the PREVIOUS frame's ``Objects`` (-1: started); votes
+# int32 [n], the previous object's pixels that the field carried onto this one; pixels int32 [n], the previous object's
+# pixels with a valid motion, moving of them marked by the ego stage's mask, own_pixels of them counted in ``own``;
+# motion fp32 [n,3], the mean 3-D displacement (X, Y, Z) of those pixels from the previous frame to this one in the unit
+# of calib, and own fp32 [n,3], the same after the camera's own motion is taken out (NaN rows: a started track; own also
+# without ``egomotion=`` or without a good ego fit).
+Tracks = namedtuple("Tracks", "n continued started ended track age prev votes pixels moving own_pixels motion own")
+
+
+def tracks_from_buffers(trk_count, trk_i, trk_f):
+    """trk_count int32 [4], trk_i int32 [max_objects,8] and trk_f fp32 [max_objects,8] of codd_track_objects
+    (include/codd_hip.h) -> ``Tracks``, the tables sliced to the n objects (copies: the buffers may be reused)."""
+    c, ti, tf = np.asarray(trk_count, np.int32), np.asarray(trk_i, np.int32), np.asarray(trk_f, np.float32)
+    n = int(c[0])
+    return Tracks(n, int(c[1]), int(c[2]), int(c[3]), *(ti[:n, k].copy() for k in range(7)), tf[:n, 0:3].copy(),
+                  tf[:n, 3:6].copy())
 
 
 def _unit_up(up, pitch_deg=0.0):
@@ -432,6 +460,32 @@ def _check_objects(objects, ground=True):
     return p
 
 
+def _check_tracks(tracks, objects=None, estimator=None):
+    """False / None -> None; True -> the defaults; a dict overrides them.  ValueError otherwise, for ``tracks`` without
+    ``objects`` (the checked dict of ``_check_objects``) or with more than ``ops.TRACK_MAX`` objects, and for an
+    estimator without a motion stage (no device call)."""
+    if tracks is None or tracks is False:
+        return None
+    if not (tracks is True or isinstance(tracks, dict)):
+        raise ValueError(f"tracks: False, True or a dict of {tuple(TRACK_DEFAULTS)} expected, got {tracks!r}")
+    if objects is None or objects is False:
+        raise ValueError("tracks: needs objects= (the tracks are those of the objects stage's objects)")
+    if getattr(estimator, "motion", None) is None:
+        raise ValueError(f"tracks={tracks!r} needs an estimator with a motion stage (this one has none)")
+    m = OBJECT_DEFAULTS["max_objects"] if objects is True else objects.get("max_objects", OBJECT_DEFAULTS["max_objects"])
+    if m > ops.TRACK_MAX:
+        raise ValueError(f"tracks: objects max_objects <= {ops.TRACK_MAX} expected, got {m!r}")
+    if tracks is True:
+        return dict(TRACK_DEFAULTS)
+    unknown = set(tracks) - set(TRACK_DEFAULTS)
+    if unknown:
+        raise ValueError(f"tracks: unknown keys {sorted(unknown)}; known: {tuple(TRACK_DEFAULTS)}")
+    p = dict(TRACK_DEFAULTS, **tracks)
+    if not (isinstance(p["min_votes"], int) and not isinstance(p["min_votes"], bool) and p["min_votes"] >= 1):
+        raise ValueError(f"tracks: an integer min_votes >= 1 expected, got {p['min_votes']!r}")
+    return p
+
+
 def select_mask(names):
     """The ``select`` bit set of codd_objects for label names of ``OBJECT_LABELS``."""
     return sum({1 << OBJECT_LABELS[v] for v in names})
@@ -567,7 +621,8 @@ class LiveSession:
 
     ``egomotion`` (False, True, or a dict overriding ``iters``, ``delta_px``, ``tau_px``, ``min_valid``): ``pop`` and
     ``step`` also return an ``Ego`` (or None for a frame without a field).  The tuple order is fixed:
-    ``result[, motion][, ego][, confidence][, aligned][, epipolar][, ground][, objects]``, each part present iff requested.
+    ``result[, motion][, ego][, confidence][, aligned][, epipolar][, ground][, objects][, tracks]``, each part present iff
+    requested.
 
     ``confidence`` (False, True, or a dict overriding ``occ_px`` (1.0 pixel) and ``tau`` (24.0 grey levels)): ``pop`` and
     ``step`` also return a ``Confidence(flags, residual)`` on the CURRENT frame's grid, for every frame (never None).  It
@@ -630,12 +685,23 @@ class LiveSession:
     frame, the ``height`` range above the floor and the ``disparity`` range; ``map`` True also returns ``ids`` uint16
     [h,w], the object number of every pixel (0xFFFF: none).  A frame without a floor has no objects.  Defined in
     include/codd_hip.h (codd_objects).
+
+    ``tracks`` (False, True, or a dict overriding ``TRACK_DEFAULTS``; needs ``objects`` with ``max_objects`` <= 1024 and an
+    estimator with a motion stage, ValueError without): ``pop`` and ``step`` also return a ``Tracks``, for every frame
+    (never None), last in the tuple; its rows belong to the rows of the frame's ``Objects``.  Every pixel of a previous
+    object is carried by the frame's SE3 field onto this frame's objects and votes; object b continues the track of the
+    previous object a iff each is the other's best match and at least ``min_votes`` pixels say so, so that a split or a
+    merge leaves the id with the larger part; every other object starts a track with a new id.  ``motion`` is the mean
+    3-D displacement of the previous object's pixels in the unit of ``calib`` and, with ``egomotion``, ``own`` is what is
+    left after the camera's motion and ``moving`` counts the pixels of the ego stage's mask.  On a frame without a
+    field (the first of a sequence) every object starts a track; ``reset()`` also restarts the ids at 1.  It needs
+    neither ``motion=`` nor ``egomotion=``.  Defined in include/codd_hip.h (codd_track_objects).
     """
 
     def __init__(self, estimator, shape, intrinsics=None, calib=None, output="depth",
                  bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False,
                  pixel_format="rgb8", yuv="bt601", pitch=None, calibration=None, zoom=1.0, align_to=None, align=None,
-                 epipolar=False, ground=False, objects=False):
+                 epipolar=False, ground=False, objects=False, tracks=False):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
@@ -649,6 +715,7 @@ class LiveSession:
         self.epi = _check_epi(epipolar)
         self.ground = _check_ground(ground)
         self.objects = _check_objects(objects, self.ground)
+        self.tracks = _check_tracks(tracks, self.objects, estimator)
         h, w = int(shape[0]), int(shape[1])
         if h <= 0 or w <= 0:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
@@ -702,13 +769,14 @@ class LiveSession:
         self.metas[0]["calib"] = self.calib
         self.motion = motion
         self._world = np.eye(4)  # camera_to_world of the last collected frame
-        if motion is not None or self.ego is not None:
+        if motion is not None or self.ego is not None or self.tracks is not None:
             from .motion import Motion
             self._K = [float(np.float32(v)) for v in self.metas[0]["intrinsics"]]  # as Motion.forward passes them
             self._bf = Motion._bf(self.metas)
         self.runner = FrameRunner(estimator, self.metas, use_graph=use_graph)
         self._open_done = False
         self._pushed = 0
+        self._track_fresh = True  # the next frame is the first of a sequence for the tracks' state
         self._inflight = deque()  # slots, oldest first
         self._ready = deque()  # results popped on the caller's behalf by a push that found the pipeline full
 
@@ -734,7 +802,7 @@ class LiveSession:
                                    for p in self._maps_host)
             self._d_out = torch.empty(h, w, dtype=odt, device=dev)
             self._h_out = [torch.empty(h, w, dtype=odt, pin_memory=True) for _ in range(DEPTH)]
-            if self.motion is not None or self.ego is not None:
+            if self.motion is not None or self.ego is not None or self.tracks is not None:
                 self._depth_prev = torch.zeros(H, W, dtype=torch.float32, device=dev)  # (rolled before it is ever read)
             if self.ego is not None:
                 self._d_ego = (torch.zeros(16, dtype=torch.float32, device=dev),
@@ -785,9 +853,20 @@ class LiveSession:
                                    torch.zeros(m, 8, dtype=torch.float32, device=dev)]
                 if self.objects["map"]:
                     self._d_objects.append(torch.empty(h, w, dtype=torch.uint16, device=dev))
+                elif self.tracks is not None:  # (the tracks read the id map on the device; it is not downloaded)
+                    self._track_ids = torch.empty(h, w, dtype=torch.uint16, device=dev)
                 self._h_objects = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_objects]
                                    for _ in range(DEPTH)]
                 self._objects_scratch = torch.empty(ops.objects_scratch(h, w, m), dtype=torch.uint8, device=dev)
+            if self.tracks is not None:
+                m = self.objects["max_objects"]
+                self._d_tracks = [torch.zeros(4, dtype=torch.int32, device=dev),
+                                  torch.zeros(m, 8, dtype=torch.int32, device=dev),
+                                  torch.zeros(m, 8, dtype=torch.float32, device=dev)]
+                self._h_tracks = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_tracks]
+                                  for _ in range(DEPTH)]
+                self._track_state = torch.zeros(ops.track_state_bytes(h, w, m), dtype=torch.uint8, device=dev)
+                self._track_scratch = torch.empty(ops.track_scratch(h, w, m), dtype=torch.uint8, device=dev)
             self._s_up, self._s_down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             ev = lambda: [torch.cuda.Event() for _ in range(DEPTH)]  # noqa: E731
             self._e_up, self._e_ingest, self._e_export, self._e_down = ev(), ev(), ev(), ev()
@@ -864,10 +943,10 @@ class LiveSession:
                                  **self._ground_par)
             if self.objects is not None:
                 ops.objects(disp, self._epi_K, self.calib, self.shape, self._d_ground[1], self._d_ground[0],
-                            *self._d_objects[:3], ids=self._d_objects[3] if self.objects["map"] else None,
-                            scratch=self._objects_scratch, **self._objects_par)
+                            *self._d_objects[:3], ids=self._object_ids(), scratch=self._objects_scratch,
+                            **self._objects_par)
             Ts = None
-            if self.motion is not None or self.ego is not None:
+            if self.motion is not None or self.ego is not None or self.tracks is not None:
                 Ts = self.runner.last.get("Ts")  # None: the frame has no field (first of a sequence) -- roll only
             if self.ego is not None:
                 if Ts is not None:  # (before export_motion rolls the depth map the field refers to)
@@ -875,11 +954,20 @@ class LiveSession:
                     ops.ego_motion(Ts, self._depth_prev, self._K, self.shape, rec, mov, res, scale=self.calib / self._bf,
                                    scratch=self._ego_scratch, **self.ego)
                 self._has_ego[k] = Ts is not None
+            if self.tracks is not None:  # (after the ego fit it reads, before export_motion rolls the depth map)
+                with_ego = self.ego is not None and Ts is not None
+                ops.track_objects(Ts, self._depth_prev, self._K, self.shape, self._object_ids(), self._d_objects[0],
+                                  self._track_state, *self._d_tracks, scratch=self._track_scratch,
+                                  ego_record=self._d_ego[0] if with_ego else None,
+                                  moving=self._d_ego[1] if with_ego else None, scale=self.calib / self._bf,
+                                  fresh=self._track_fresh, min_votes=self.tracks["min_votes"],
+                                  max_objects=self.objects["max_objects"])
+                self._track_fresh = False
             if self.motion is not None:
                 ops.export_motion(Ts, disp, self._depth_prev, self._d_mot, self.motion, self._K, self._bf,
                                   scale=self.calib / self._bf)
                 self._has_mot[k] = Ts is not None
-            elif self.ego is not None:
+            elif self.ego is not None or self.tracks is not None:
                 ops.export_motion(None, disp, self._depth_prev, None, "sceneflow", self._K, self._bf, crop=self.shape)
             self._e_export[k].record(compute)
             with torch.cuda.stream(self._s_down):
@@ -904,6 +992,9 @@ class LiveSession:
                         host.copy_(dev_buf, non_blocking=True)
                 if self.objects is not None:
                     for host, dev_buf in zip(self._h_objects[k], self._d_objects):
+                        host.copy_(dev_buf, non_blocking=True)
+                if self.tracks is not None:
+                    for host, dev_buf in zip(self._h_tracks[k], self._d_tracks):
                         host.copy_(dev_buf, non_blocking=True)
                 self._e_down[k].record(self._s_down)
         self._inflight.append(k)
@@ -932,7 +1023,15 @@ class LiveSession:
         if self.objects is not None:
             got = [t.numpy() for t in self._h_objects[k]]  # (objects_from_buffers copies what it keeps)
             out.append(objects_from_buffers(got[0], got[1], got[2], got[3].copy() if self.objects["map"] else None))
+        if self.tracks is not None:
+            out.append(tracks_from_buffers(*(t.numpy() for t in self._h_tracks[k])))  # (copies what it keeps)
         return out[0] if len(out) == 1 else tuple(out)
+
+    def _object_ids(self):
+        """The device id map codd_objects writes: the downloaded one, the tracks' own, or None."""
+        if self.objects["map"]:
+            return self._d_objects[3]
+        return self._track_ids if self.tracks is not None else None
 
     def _ground_bufs(self, bufs):
         """(record, labels, height, grid_count, grid_height) of the buffers present, None for the others."""
@@ -953,7 +1052,8 @@ class LiveSession:
         """The oldest frame's result: numpy [h,w] (fp32, or uint16 for ``disp_u16``), owned by the caller; with a
         ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None; with ``egomotion``, an ``Ego`` or None
         follows; with ``confidence``, a ``Confidence``; with ``align_to``, an ``Aligned``; with ``epipolar``, an
-        ``Epipolar``; with ``ground``, a ``Ground``; with ``objects``, an ``Objects`` comes last."""
+        ``Epipolar``; with ``ground``, a ``Ground``; with ``objects``, an ``Objects``; with ``tracks``, a ``Tracks`` comes
+        last."""
         if self._ready:
             return self._ready.popleft()
         if not self._inflight:
@@ -976,6 +1076,7 @@ class LiveSession:
         captured graph is kept."""
         self.runner.reset()
         self.est.reset_inference_state()
+        self._track_fresh = True
 
     def close(self):
         if self._open_done:
@@ -985,7 +1086,8 @@ class LiveSession:
             for name in ("_h_in", "_d_in", "_scratch", "_maps", "_d_out", "_h_out", "_depth_prev", "_d_mot", "_h_mot",
                          "_d_ego", "_h_ego", "_ego_scratch", "_d_conf", "_h_conf", "_d_align", "_h_align",
                          "_d_epi", "_h_epi", "_epi_scratch", "_d_ground", "_h_ground", "_ground_scratch",
-                         "_d_objects", "_h_objects", "_objects_scratch"):
+                         "_d_objects", "_h_objects", "_objects_scratch", "_track_ids", "_d_tracks", "_h_tracks",
+                         "_track_state", "_track_scratch"):
                 setattr(self, name, None)
             self._open_done = False
         self._inflight.clear()

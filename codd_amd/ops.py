@@ -2200,6 +2200,77 @@ def objects(disp, K, calib, crop, labels, ground_record, count, obj_i, obj_f, id
     return count
 
 
+TRACK_PARAMS = dict(min_votes=16)
+TRACK_MAX = 1024  # CODD_TRACK_MAX_OBJECTS of include/codd_hip.h
+
+
+def _track_sizes(h, w, max_objects, what):
+    h, w, m = int(h), int(w), int(max_objects)
+    if h <= 0 or w <= 0 or h * w >= 2 ** 31 or not 1 <= m <= TRACK_MAX:
+        raise ValueError(f"{what}: positive (h, w) with h w < 2^31 and max_objects in [1, {TRACK_MAX}] expected, "
+                         f"got {(h, w)}, {max_objects}")
+    return h, w, m
+
+
+def track_state_bytes(h, w, max_objects=256):
+    """Bytes of the persistent state ``track_objects`` keeps for an h x w crop (codd_track_state_bytes)."""
+    return int(_abi.load().codd_track_state_bytes(*_track_sizes(h, w, max_objects, "track_state_bytes")))
+
+
+def track_scratch(h, w, max_objects=256):
+    """Bytes of scratch ``track_objects`` needs for an h x w crop (codd_track_scratch)."""
+    return int(_abi.load().codd_track_scratch(*_track_sizes(h, w, max_objects, "track_scratch")))
+
+
+def track_objects(T, depth_prev, K, crop, ids, count, state, trk_count, trk_i, trk_f, scratch=None, ego_record=None,
+                  moving=None, scale=1.0, fresh=False, min_votes=16, max_objects=256):
+    """Which object of this frame is which object of the last one, and how did it move?  Every pixel of a previous object
+    (the id map in ``state``) is carried by the SE3 field ``T`` [1,H,W,7] (None: the frame has no field and every object
+    starts a track) over the ``crop`` (h, w) of the previous frame's depth ``depth_prev`` [H,W] (read only; call this
+    before ``export_motion`` rolls it) onto ``ids`` uint16 [h,w] and ``count`` int32 [4], the device outputs of this
+    frame's ``objects``, and votes; mutual best matches with at least ``min_votes`` votes keep their track id
+    (include/codd_hip.h, codd_track_objects).  ``ego_record`` fp32 [16] and ``moving`` uint8 [h,w] (both optional) are the
+    device outputs of ``ego_motion``.  ``state``: a uint8 tensor of ``track_state_bytes`` bytes the caller keeps between
+    calls; ``fresh`` True ignores its contents (the first frame of a sequence).  Outputs are caller-owned device tensors:
+    ``trk_count`` int32 [4] (n, continued, started, ended); ``trk_i`` int32 [max_objects,8] (track, age, prev, votes,
+    pixels, moving, own_pixels, 0); ``trk_f`` fp32 [max_objects,8] (Dx, Dy, Dz, Ox, Oy, Oz, 0, 0), the mean displacement of
+    the object's pixels and what is left of it after the camera's motion, NaN where undefined; rows past the objects
+    zero.  ``scratch``: a uint8 tensor of ``track_scratch`` bytes; allocated here when None.  4 launches on the current
+    stream, no host synchronisation."""
+    h, w, m = _track_sizes(crop[0], crop[1], max_objects, "track_objects")
+    if not (isinstance(min_votes, int) and not isinstance(min_votes, bool) and min_votes >= 1):
+        raise ValueError(f"track_objects: an integer min_votes >= 1 expected, got {min_votes!r}")
+    if T is not None and depth_prev is None:
+        raise ValueError("track_objects: T needs depth_prev")
+    _require_gpu(ids)
+    lib = _abi.load()
+    H, W = (h, w) if depth_prev is None else depth_prev.shape[-2:]
+    if T is not None:
+        assert T.dtype == torch.float32 and T.is_cuda and T.is_contiguous() and T.numel() == H * W * 7 and T.shape[-1] == 7
+    if depth_prev is not None:
+        assert depth_prev.dtype == torch.float32 and depth_prev.is_cuda and depth_prev.is_contiguous() and depth_prev.numel() == H * W
+    assert ids.dtype == torch.uint16 and ids.is_cuda and ids.is_contiguous() and tuple(ids.shape) == (h, w)
+    assert count.dtype == torch.int32 and count.is_cuda and count.is_contiguous() and count.numel() == 4
+    assert trk_count.dtype == torch.int32 and trk_count.is_cuda and trk_count.is_contiguous() and trk_count.numel() == 4
+    assert trk_i.dtype == torch.int32 and trk_i.is_cuda and trk_i.is_contiguous() and tuple(trk_i.shape) == (m, 8)
+    assert trk_f.dtype == torch.float32 and trk_f.is_cuda and trk_f.is_contiguous() and tuple(trk_f.shape) == (m, 8)
+    if ego_record is not None:
+        assert ego_record.dtype == torch.float32 and ego_record.is_cuda and ego_record.is_contiguous() and ego_record.numel() == 16
+    if moving is not None:
+        assert moving.dtype == torch.uint8 and moving.is_cuda and moving.is_contiguous() and tuple(moving.shape) == (h, w)
+    assert state.dtype == torch.uint8 and state.is_cuda and state.is_contiguous()
+    if scratch is None:
+        scratch = torch.empty(track_scratch(h, w, m), dtype=torch.uint8, device=ids.device)
+    assert scratch.dtype == torch.uint8 and scratch.is_cuda and scratch.is_contiguous()
+    _abi.check(lib.codd_track_objects(None if T is None else T.data_ptr(), None if depth_prev is None else depth_prev.data_ptr(),
+                                      H, W, h, w, *[float(v) for v in K], float(scale), ids.data_ptr(), count.data_ptr(),
+                                      None if ego_record is None else ego_record.data_ptr(),
+                                      None if moving is None else moving.data_ptr(), int(min_votes), m, int(bool(fresh)),
+                                      state.data_ptr(), state.numel(), scratch.data_ptr(), scratch.numel(),
+                                      trk_count.data_ptr(), trk_i.data_ptr(), trk_f.data_ptr(), _stream()), "track_objects")
+    return trk_count
+
+
 ALIGN_MAX_FOOTPRINT = 4  # CODD_ALIGN_MAX_FOOTPRINT of include/codd_hip.h
 
 

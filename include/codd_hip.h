@@ -1030,6 +1030,73 @@ int codd_objects(const float* disp, int H, int W, int h, int w, float fx, float 
                  int min_pixels, float min_height, int max_objects, void* scratch, long long scratch_bytes, int* count,
                  int* obj_i, float* obj_f, unsigned short* ids, void* stream);
 
+/* Live-session object tracks (codd_amd/live.py, tracks=): persistent track ids for the objects of codd_objects across
+ * frames, and per object the mean 3-D displacement of its pixels under the frame's SE3 field.  The reference has no such
+ * output; this replaces downloading both id maps and a flow map every frame, warping one id map onto the other on the
+ * host and counting overlaps with np.add.at.  4 launches, no allocation, no host synchronisation, no launch count or grid
+ * that depends on the data, integer atomics only: equal inputs give equal bytes.
+ * T [H,W,7] and depth_prev [H,W] as codd_ego_motion takes them, read inside the h x w crop only; depth_prev is not written
+ * (codd_export_motion rolls it; call this first).  T == NULL: the frame has no field; nothing is associated, every
+ * current object starts a track and the ids keep counting.  K = (fx, fy, cx, cy) at full resolution; scale as
+ * codd_ego_motion's.  ids_cur uint16 [h,w] and count int32 [4]: the DEVICE outputs of this frame's codd_objects;
+ * n_cur = min(count[0], max_objects) (a negative count[0] counts as 0).  ego_record (may be NULL): the DEVICE pointer to
+ * the 16 fp32 of codd_ego_motion.  moving [h,w] (may be NULL): its mask.
+ * state: caller-owned, persistent between calls, codd_track_state_bytes(h, w, max_objects) bytes of any alignment.  Its
+ * layout starts at the first 16-byte boundary at or after the pointer (pass the same pointer every call):
+ *   int32 hdr[8] = (n_prev, next_id, frames, 0, 0, 0, 0, 0);
+ *   int32 [max_objects,2] = (track, age) of the previous frame's objects, rows >= n_prev zero;
+ *   uint16 [h w], the previous frame's id map.
+ * fresh != 0: the state's contents are irrelevant; n_prev = 0, next_id = 1, frames = 0.  Otherwise n_prev is hdr[0] clamped
+ * to [0, max_objects].
+ * Every operation below is one fp32 operation rounded on its own (no fused multiply-add; division correctly rounded)
+ * unless it says fp64.
+ *   per pixel   p = (x, y) of the crop, on the PREVIOUS frame's grid: a = state.ids[p]; the pixel is skipped if a == 0xFFFF
+ *               or a >= n_prev.  X0 = inv_project(depth_prev[y,x], x, y, K); X1 = se3_act(T[y,x], X0) (qrot, then + t);
+ *               c = project(X1): the expressions of codd_amd/csrc/se3.h in the order written there (PEPS and MIN_DEPTH as
+ *               in projective_ops.py:7-8).  The pixel is VALID iff X0.z >= MIN_DEPTH && X1.z >= MIN_DEPTH and all six
+ *               coordinates are finite (codd_ego_motion's rule); an invalid pixel adds nothing and does not vote.
+ *   landing     u = floorf(c.x + 0.5f); v = floorf(c.y + 0.5f).  A valid pixel LANDS iff 0 <= u < w && 0 <= v < h, compared
+ *               as floats (false for NaN); then b = ids_cur[v,u] and the pixel VOTES for (a, b) iff b < n_cur.
+ *   motion      D_k = scale * (X1.k - X0.k), k = x, y, z.  If ego_record != NULL && ego_record[7] != 0: Y = qrot(q =
+ *               ego_record[3:7], X0) and O_k = scale * (X1.k - Y.k) - ego_record[k], what is left after the camera's motion.
+ *               Q(v) = llrint((double)fminf(fmaxf(v, -4096.f), 4096.f) * 262144.0) (ties to even; fmaxf and fminf return
+ *               the other operand for a NaN, which therefore quantises as -4096).  Sums of at most 2^31 such values fit an
+ *               int64.
+ *   sums        per previous object a, over its valid pixels, in integers: V[a][b] the votes; n_a the valid pixels;
+ *               S_a[3] = sum Q(D); So_a[3] = sum Q(O) and no_a their number, accumulated only with a good ego record;
+ *               mv_a the valid pixels with moving[p] == 1 (0 without moving).
+ *   association best_cur(a): the b with the largest V[a][b] > 0, ties to the smallest b; best_prev(b): the a with the
+ *               largest V[a][b] > 0, ties to the smallest a.  Object b CONTINUES a iff best_prev(b) == a && best_cur(a)
+ *               == b && V[a][b] >= min_votes: after a split or a merge the id stays with the larger part.  A continued
+ *               object keeps a's track id with age + 1; every other object STARTS a track: starting objects take
+ *               next_id, next_id + 1, .. in ascending b, with age 1.  If next_id > 2^31 - 1 - max_objects (or < 1) at
+ *               the start of a call it restarts at 1; track id 0 is never given.
+ *   outputs     caller-owned device buffers; rows >= n_cur are zero, cleared on every call.  trk_count int32 [4]: (n_cur,
+ *               continued, started, ended); ended = n_prev - continued, the previous objects that nothing continues.
+ *               trk_i int32 [max_objects,8]: (track, age, prev, votes, pixels, moving, own_pixels, 0) = (.., a, V[a][b],
+ *               n_a, mv_a, no_a, 0); a started track has prev = -1 and zeros in columns 3 to 6.  trk_f fp32
+ *               [max_objects,8]: (Dx, Dy, Dz, Ox, Oy, Oz, 0, 0) with D = (float)(((double)S_a / (double)n_a) / 262144.0)
+ *               and O likewise over no_a (fp64 divisions, one rounding to fp32); D is NaN for a started track or n_a ==
+ *               0, O for a started track or no_a == 0 (which covers a call without a good ego record).
+ *   roll        the state becomes: hdr = (n_cur, next_id + started, frames + 1, 0..); the (track, age) table of the
+ *               current objects, rows >= n_cur zero; ids_cur copied into the id map (by the lane that read the old
+ *               element, in the per-pixel launch).
+ * scratch: codd_track_scratch(h, w, max_objects) bytes, contents irrelevant, any alignment: the vote matrix
+ * (max_objects^2 int32, 4 MB at the limit), the per-object sums and the row and column maxima.  Both size functions
+ * return -1 for a non-positive h or w, h w >= 2^31 or max_objects outside [1, CODD_TRACK_MAX_OBJECTS].  No pointer needs
+ * more than its element's alignment.
+ * CODD_EINVAL, before any launch: ids_cur, count, state, scratch, trk_count, trk_i or trk_f NULL; T without depth_prev; a
+ * non-positive size, h > H, w > W or h w >= 2^31; max_objects outside [1, 1024]; min_votes < 1; fx, fy or scale not finite
+ * and > 0; cx or cy not finite; state_bytes or scratch_bytes below its size function's answer. */
+#define CODD_TRACK_MAX_OBJECTS 1024
+long long codd_track_state_bytes(int h, int w, int max_objects);
+long long codd_track_scratch(int h, int w, int max_objects);
+int codd_track_objects(const float* T, const float* depth_prev, int H, int W, int h, int w, float fx, float fy, float cx,
+                       float cy, float scale, const unsigned short* ids_cur, const int* count, const float* ego_record,
+                       const unsigned char* moving, int min_votes, int max_objects, int fresh, void* state,
+                       long long state_bytes, void* scratch, long long scratch_bytes, int* trk_count, int* trk_i,
+                       float* trk_f, void* stream);
+
 /* Ablation plug-ins.  codd_fusion_select: mode 0 = KalmanFusion (model/fusion/others.py:124-153; constant
  * gain K = Q/(Q+R), the reference never updates P), mode 1 = GTFusion (:54-86; gt [B,1,hg,wg], zero-padded).
  * cur, warp, out: [B,1,H,W]. */
