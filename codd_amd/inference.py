@@ -89,6 +89,12 @@ def parse_args(argv=None):
                         "with zeros to MAX = the session's max_objects, track, age, prev, votes, pixels, moving and "
                         "own_pixels [1, frames, MAX] and motion and own [1, frames, MAX, 3] (row k belongs to object k of "
                         "<name>.objects.pred.npz; NaN: a started track, own also without --ego)")
+    p.add_argument("--scan", action="store_true",
+                   help="--ground: a planar range scan over the camera's horizontal field (how far to the first obstacle in "
+                        "every direction); also write <name>.scan.pred.npz: ranges and free fp32 and object int32 [1, frames, "
+                        "beams] (range +inf: clear as far as the floor was seen, NaN: unknown; object -1: none, or no "
+                        "--objects), hits, clear, unknown and obstacle_pixels [1, frames], angle_min, angle_increment "
+                        "(radians), range_min and range_max")
     p.add_argument("--align-footprint", type=int, default=None, choices=[1, 2, 3, 4],
                    help="--align: target pixels per source pixel and axis (default: the smallest that leaves no hole lines)")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
@@ -146,6 +152,8 @@ def parse_args(argv=None):
         p.error("--objects needs --ground")
     if args.tracks and not args.objects:
         p.error("--tracks needs --objects")
+    if args.scan and not args.ground:
+        p.error("--scan needs --ground")
     if args.ground_grid is not None:
         m = re.fullmatch(r"(\d+)x(\d+)", args.ground_grid)
         if not m or not int(m.group(1)) or not int(m.group(2)):
@@ -320,7 +328,8 @@ def run_live(args, model, videos):
     line with the frames in which a floor was found is printed with or without --show) and, with --objects,
     <name>.objects.pred.npz (per-frame n, found and the object tables padded to max_objects, written with or without
     --show; the id maps with --show only) and, with --tracks, <name>.tracks.pred.npz (per-frame n, continued, started, ended
-    and the track tables padded to max_objects, written with or without --show).  With --pixel-format the
+    and the track tables padded to max_objects, written with or without --show) and, with --scan, <name>.scan.pred.npz
+    (per-frame ranges, free ranges, objects and counts, written with or without --show).  With --pixel-format the
     frame files are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU.  With
     --calibration the frames (files or --frame-size) have the calibration's source size and every result has --net-size."""
     from PIL import Image
@@ -348,6 +357,8 @@ def run_live(args, model, videos):
         extra["objects"] = dict(map=bool(args.show))
     if getattr(args, "tracks", False):
         extra["tracks"] = True
+    if getattr(args, "scan", False):
+        extra["scan"] = True
     raw = getattr(args, "pixel_format", None)
     if raw:
         extra.update(pixel_format=raw, pitch=args.pitch, yuv=args.yuv or "bt601")
@@ -387,11 +398,14 @@ def run_live(args, model, videos):
             if align_to:
                 aligned = _NpzStream(osp.join(args.show_dir, name + ".aligned.pred.npz"), "depth",
                                      (1, nf) + s.align_target.camera.size, np.float32)
-        n, epis, grounds, objs, trks = 0, [], [], [], []
+        n, epis, grounds, objs, trks, scans = 0, [], [], [], [], []
         try:
             frames = iter_raw_frames(lefts, rights, raw, src, args.pitch) if raw else iter_frames(lefts, rights)
             for res in live_results(s, frames):
                 n += 1
+                if "scan" in extra:
+                    res, sc = res[:-1], res[-1]  # (a Ground precedes it: still a tuple)
+                    scans.append(sc)
                 if "tracks" in extra:
                     res, tr = res[:-1], res[-1]  # (a Ground and an Objects precede it: still a tuple)
                     trks.append(tr)
@@ -501,6 +515,21 @@ def run_live(args, model, videos):
             print(f"{name}: tracks: {sum(tr.started for tr in trks)} started, {sum(tr.continued for tr in trks)} continued, "
                   f"{sum(tr.ended for tr in trks)} ended in {len(trks)} frames"
                   + (f", oldest {max((int(tr.age.max()) for tr in trks if tr.n), default=0)} frames" if trks else ""))
+        if "scan" in extra:
+            os.makedirs(args.show_dir, exist_ok=True)
+            beams = s.scan["beams"]
+            np.savez(osp.join(args.show_dir, name + ".scan.pred.npz"),
+                     ranges=np.array([[sc.ranges for sc in scans]], np.float32).reshape(1, len(scans), beams),
+                     free=np.array([[sc.free for sc in scans]], np.float32).reshape(1, len(scans), beams),
+                     object=np.array([[sc.object for sc in scans]], np.int32).reshape(1, len(scans), beams),
+                     **{k: np.array([[getattr(sc, k) for sc in scans]], np.int32) for k in ("hits", "clear", "unknown",
+                                                                                           "obstacle_pixels")},
+                     **{k: np.array(v, np.float64) for k, v in zip(("angle_min", "angle_increment", "range_min", "range_max"),
+                                                                   s._scan_meta)})
+            near = [float(sc.ranges[np.isfinite(sc.ranges)].min()) for sc in scans if sc.hits]
+            print(f"{name}: scan: {beams} beams; {sum(sc.hits for sc in scans)} hits, {sum(sc.clear for sc in scans)} clear, "
+                  f"{sum(sc.unknown for sc in scans)} unknown in {len(scans)} frames"
+                  + (f", nearest hit {min(near):.3f}" if near else ""))
         print(f"{name}: {n} frames")
     for s in sessions.values():
         s.close()

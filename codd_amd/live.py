@@ -63,6 +63,12 @@ across frames and how each one moves: ``codd_track_objects`` runs after ``codd_e
 ``codd_export_motion`` rolls the previous depth map, carries every pixel of the previous frame's objects along the SE3
 field onto this frame's id map, lets it vote, and keeps a track id where the best matches are mutual; per object it
 returns the mean 3-D displacement of its pixels and, with ``egomotion=``, what is left of it after the camera's own motion.
+
+With ``scan=`` (which needs ``ground=``) the session says how far one can go in every direction in front of the camera:
+``codd_range_scan`` runs right after ``codd_objects`` (after ``codd_ground_plane`` without ``objects=``) on the same device
+labels, record and id map, bins the floor and obstacle pixels by bearing and range in the frame of the objects' extents,
+and returns a planar laser scan -- per beam the range of the first obstacle, the pixel and the object that made it, and
+how far the floor was seen in front of it.
 """
 from collections import deque, namedtuple
 
@@ -88,6 +94,7 @@ GROUND_DEFAULTS = dict(step=2, iters=8, delta_px=0.25, delta0_px=4.0, asym=4.0, 
 OBJECT_DEFAULTS = dict(select=("obstacle",), gap_px=1.0, gap_rel=0.05, min_pixels=64, min_height=0.15, max_objects=256,
                        map=False)
 TRACK_DEFAULTS = dict(min_votes=16)
+SCAN_DEFAULTS = dict(beams=256, angles_deg=None, range_min=0.0, range_max=12.8, bins=128, select=("obstacle",), min_pixels=8)
 OBJECT_LABELS = dict(floor=ops.GROUND_FLOOR, obstacle=ops.GROUND_OBSTACLE, overhead=ops.GROUND_OVERHEAD,
                      below=ops.GROUND_BELOW)  # the names ``select`` takes
 
@@ -194,6 +201,36 @@ def tracks_from_buffers(trk_count, trk_i, trk_f):
     n = int(c[0])
     return Tracks(n, int(c[1]), int(c[2]), int(c[3]), *(ti[:n, k].copy() for k in range(7)), tf[:n, 0:3].copy(),
                   tf[:n, 3:6].copy())
+
+
+# One frame's range scan, caller-owned, in the convention of a planar laser scan: beam k covers the bearings angle_min + k *
+# angle_increment .. angle_min + (k + 1) * angle_increment (radians from the ground grid's forward axis, positive to the
+# right); ranges fp32 [beams] in the unit of calib / fx, measured on the floor from the point under the camera: the range of
+# the nearest pixel of the first range bin holding at least min_pixels obstacle pixels, +inf where the beam is clear as far
+# as the floor was seen, NaN where nothing is known; free fp32 [beams], the range up to which the floor was seen in front of
+# the hit (0: not at all); hit_xz fp32 [beams,2], (gx, gz) of the hit pixel in the frame of Objects.extent (zeros without a
+# hit); pixel int32 [beams], its raster index y * w + x (-1 without); object int32 [beams], its number in the frame's
+# ``Objects`` (-1: none, or no objects=); track int32 [beams], the track id of that object (0: none; None without tracks=);
+# support int32 [beams], the obstacle pixels of the hit bin; floor int32 [beams], the floor pixels in front of the hit;
+# hits, clear and unknown beams (they add up to the beams) and obstacle_pixels binned in all.
+Scan = namedtuple("Scan", "angle_min angle_increment range_min range_max ranges free hit_xz pixel object track support floor "
+                          "hits clear unknown obstacle_pixels")
+
+
+def scan_from_buffers(count, scan_i, scan_f, edges_meta, tracks=None):
+    """count int32 [4], scan_i int32 [beams,4] and scan_f fp32 [beams,4] of codd_range_scan (include/codd_hip.h) ->
+    ``Scan`` (copies: the buffers may be reused).  ``edges_meta`` = (angle_min, angle_increment, range_min, range_max);
+    ``tracks``: the frame's ``Tracks`` or None -- with it ``track`` is ``tracks.track[object]``, 0 where there is no object."""
+    count, si, sf = np.asarray(count, np.int32), np.asarray(scan_i, np.int32), np.asarray(scan_f, np.float32)
+    obj = si[:, 1].copy()
+    track = None
+    if tracks is not None:
+        known = (obj >= 0) & (obj < tracks.n)
+        track = np.zeros(obj.shape, np.int32)
+        track[known] = np.asarray(tracks.track, np.int32)[obj[known]]
+    a0, da, r0, r1 = (float(v) for v in edges_meta)
+    return Scan(a0, da, r0, r1, sf[:, 0].copy(), sf[:, 1].copy(), sf[:, 2:4].copy(), si[:, 0].copy(), obj, track,
+                si[:, 2].copy(), si[:, 3].copy(), int(count[0]), int(count[1]), int(count[2]), int(count[3]))
 
 
 def _unit_up(up, pitch_deg=0.0):
@@ -486,6 +523,69 @@ def _check_tracks(tracks, objects=None, estimator=None):
     return p
 
 
+def _check_scan(scan, ground=True):
+    """False / None -> None; True -> the defaults; a dict overrides them.  ValueError otherwise, and for ``scan`` without
+    ``ground`` (no device call)."""
+    if scan is None or scan is False:
+        return None
+    if not (scan is True or isinstance(scan, dict)):
+        raise ValueError(f"scan: False, True or a dict of {tuple(SCAN_DEFAULTS)} expected, got {scan!r}")
+    if ground is None or ground is False:
+        raise ValueError("scan: needs ground= (the scan is that of the ground stage's labels, in its frame)")
+    if scan is True:
+        return dict(SCAN_DEFAULTS)
+    unknown = set(scan) - set(SCAN_DEFAULTS)
+    if unknown:
+        raise ValueError(f"scan: unknown keys {sorted(unknown)}; known: {tuple(SCAN_DEFAULTS)}")
+    p = dict(SCAN_DEFAULTS, **scan)
+    is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+    for k, hi in (("beams", ops.SCAN_MAX_BEAMS), ("bins", ops.SCAN_MAX_BINS)):
+        if not (is_int(p[k]) and 1 <= p[k] <= hi):
+            raise ValueError(f"scan: an integer {k} in [1, {hi}] expected, got {p[k]!r}")
+    if p["beams"] * p["bins"] > ops.SCAN_MAX_CELLS:
+        raise ValueError(f"scan: beams * bins <= {ops.SCAN_MAX_CELLS} expected, got {p['beams']} * {p['bins']}")
+    if not (is_int(p["min_pixels"]) and p["min_pixels"] >= 1):
+        raise ValueError(f"scan: an integer min_pixels >= 1 expected, got {p['min_pixels']!r}")
+    for k in ("range_min", "range_max"):
+        try:
+            p[k] = float(p[k])
+        except (TypeError, ValueError):
+            raise ValueError(f"scan: a number expected for {k}, got {p[k]!r}") from None
+        if not np.isfinite(p[k]):
+            raise ValueError(f"scan: a finite {k} expected, got {p[k]!r}")
+    if not p["range_max"] > 0:
+        raise ValueError(f"scan: positive range_max expected, got {p['range_max']!r}")
+    if not 0 <= p["range_min"] < p["range_max"]:
+        raise ValueError(f"scan: 0 <= range_min < range_max expected, got {p['range_min']!r}, {p['range_max']!r}")
+    sel = p["select"]
+    if isinstance(sel, str):
+        sel = (sel,)
+    if not (isinstance(sel, (tuple, list)) and len(sel) > 0 and all(isinstance(v, str) and v in OBJECT_LABELS for v in sel)):
+        raise ValueError(f"scan: select: one or more of {tuple(OBJECT_LABELS)} expected, got {p['select']!r}")
+    if "floor" in sel:
+        raise ValueError("scan: select: the floor is what the beams run over, not an obstacle")
+    p["select"] = tuple(sel)
+    if p["angles_deg"] is not None:
+        a = p["angles_deg"]
+        try:
+            a = tuple(float(v) for v in a)
+        except (TypeError, ValueError):
+            raise ValueError(f"scan: angles_deg None or two numbers expected, got {p['angles_deg']!r}") from None
+        if not (len(a) == 2 and -90.0 <= a[0] < a[1] <= 90.0):  # (NaN compares false)
+            raise ValueError(f"scan: angles_deg None or -90 <= min < max <= 90 expected, got {p['angles_deg']!r}")
+        p["angles_deg"] = a
+    return p
+
+
+def scan_span(p, K, w):
+    """(angle_min, angle_max) in radians of the checked ``scan`` dict: ``angles_deg``, or the camera's own horizontal field
+    atan((0 - cx) / fx) .. atan((w - 1 - cx) / fx)."""
+    if p["angles_deg"] is not None:
+        return float(np.deg2rad(p["angles_deg"][0])), float(np.deg2rad(p["angles_deg"][1]))  # (90 degrees: np.pi / 2 exactly)
+    fx, cx = float(K[0]), float(K[2])
+    return float(np.arctan((0.0 - cx) / fx)), float(np.arctan((float(w) - 1.0 - cx) / fx))
+
+
 def select_mask(names):
     """The ``select`` bit set of codd_objects for label names of ``OBJECT_LABELS``."""
     return sum({1 << OBJECT_LABELS[v] for v in names})
@@ -621,8 +721,8 @@ class LiveSession:
 
     ``egomotion`` (False, True, or a dict overriding ``iters``, ``delta_px``, ``tau_px``, ``min_valid``): ``pop`` and
     ``step`` also return an ``Ego`` (or None for a frame without a field).  The tuple order is fixed:
-    ``result[, motion][, ego][, confidence][, aligned][, epipolar][, ground][, objects][, tracks]``, each part present iff
-    requested.
+    ``result[, motion][, ego][, confidence][, aligned][, epipolar][, ground][, objects][, tracks][, scan]``, each part
+    present iff requested.
 
     ``confidence`` (False, True, or a dict overriding ``occ_px`` (1.0 pixel) and ``tau`` (24.0 grey levels)): ``pop`` and
     ``step`` also return a ``Confidence(flags, residual)`` on the CURRENT frame's grid, for every frame (never None).  It
@@ -696,12 +796,23 @@ class LiveSession:
     left after the camera's motion and ``moving`` counts the pixels of the ego stage's mask.  On a frame without a
     field (the first of a sequence) every object starts a track; ``reset()`` also restarts the ids at 1.  It needs
     neither ``motion=`` nor ``egomotion=``.  Defined in include/codd_hip.h (codd_track_objects).
+
+    ``scan`` (False, True, or a dict overriding ``SCAN_DEFAULTS``; needs ``ground``, ValueError without): ``pop`` and
+    ``step`` also return a ``Scan``, for every frame (never None), last in the tuple: a planar range scan of ``beams``
+    (1 .. 2048) equal beams over ``angles_deg`` = (min, max) degrees from the ground grid's forward axis, positive to the
+    right, within -90 .. 90 (None: the camera's own horizontal field).  Every floor pixel and every pixel labelled one of
+    ``select`` (names of ``OBJECT_LABELS`` other than the floor) with a range in [``range_min``, ``range_max``) on the floor
+    falls into one of ``bins`` (1 .. 1024; beams * bins <= 2^20) range bins of its beam; the first bin with at least
+    ``min_pixels`` obstacle pixels is the hit -- a lone speckle nearer than that does not stop the beam -- and ``ranges``
+    is the range of its nearest pixel; ``free`` says how far floor was seen in front of it.  With ``objects`` the hit names
+    its object, with ``tracks`` its track.  A frame without a floor has only unknown beams.  Defined in include/codd_hip.h
+    (codd_range_scan).
     """
 
     def __init__(self, estimator, shape, intrinsics=None, calib=None, output="depth",
                  bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False,
                  pixel_format="rgb8", yuv="bt601", pitch=None, calibration=None, zoom=1.0, align_to=None, align=None,
-                 epipolar=False, ground=False, objects=False, tracks=False):
+                 epipolar=False, ground=False, objects=False, tracks=False, scan=False):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
@@ -716,6 +827,7 @@ class LiveSession:
         self.ground = _check_ground(ground)
         self.objects = _check_objects(objects, self.ground)
         self.tracks = _check_tracks(tracks, self.objects, estimator)
+        self.scan = _check_scan(scan, self.ground)
         h, w = int(shape[0]), int(shape[1])
         if h <= 0 or w <= 0:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
@@ -755,6 +867,13 @@ class LiveSession:
             self._ground_par = {k: g[k] for k in ops.GROUND_PARAMS}
         if self.objects is not None:
             self._objects_par = dict({k: self.objects[k] for k in ops.OBJECT_PARAMS}, select=select_mask(self.objects["select"]))
+        if self.scan is not None:
+            sc = self.scan
+            lo, hi = scan_span(sc, self._epi_K, w)
+            self._scan_edges_host = ops.scan_edges(sc["beams"], lo, hi)  # (numpy: no device call; ValueError for an empty span)
+            self._scan_meta = (lo, (hi - lo) / sc["beams"], sc["range_min"], sc["range_max"])
+            self._scan_par = dict(range_min=sc["range_min"], range_max=sc["range_max"], bins=sc["bins"],
+                                  select=select_mask(sc["select"]), min_pixels=sc["min_pixels"])
         self.src_shape = (h, w) if self.rect is None else self.rect.size  # the size of a frame as the camera hands it out
         # (rows, row_bytes, pitch, nbytes) of a source frame; ValueError if invalid
         self._layout = frame_layout(pixel_format, self.src_shape[0], self.src_shape[1], pitch)
@@ -853,7 +972,7 @@ class LiveSession:
                                    torch.zeros(m, 8, dtype=torch.float32, device=dev)]
                 if self.objects["map"]:
                     self._d_objects.append(torch.empty(h, w, dtype=torch.uint16, device=dev))
-                elif self.tracks is not None:  # (the tracks read the id map on the device; it is not downloaded)
+                elif self.tracks is not None or self.scan is not None:  # (read on the device; it is not downloaded)
                     self._track_ids = torch.empty(h, w, dtype=torch.uint16, device=dev)
                 self._h_objects = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_objects]
                                    for _ in range(DEPTH)]
@@ -867,6 +986,15 @@ class LiveSession:
                                   for _ in range(DEPTH)]
                 self._track_state = torch.zeros(ops.track_state_bytes(h, w, m), dtype=torch.uint8, device=dev)
                 self._track_scratch = torch.empty(ops.track_scratch(h, w, m), dtype=torch.uint8, device=dev)
+            if self.scan is not None:
+                beams = self.scan["beams"]
+                self._d_scan = [torch.zeros(4, dtype=torch.int32, device=dev),
+                                torch.zeros(beams, 4, dtype=torch.int32, device=dev),
+                                torch.zeros(beams, 4, dtype=torch.float32, device=dev)]
+                self._h_scan = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_scan]
+                                for _ in range(DEPTH)]
+                self._scan_edges = torch.from_numpy(self._scan_edges_host).to(dev)
+                self._scan_scratch = torch.empty(ops.range_scan_scratch(beams, self.scan["bins"]), dtype=torch.uint8, device=dev)
             self._s_up, self._s_down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             ev = lambda: [torch.cuda.Event() for _ in range(DEPTH)]  # noqa: E731
             self._e_up, self._e_ingest, self._e_export, self._e_down = ev(), ev(), ev(), ev()
@@ -945,6 +1073,10 @@ class LiveSession:
                 ops.objects(disp, self._epi_K, self.calib, self.shape, self._d_ground[1], self._d_ground[0],
                             *self._d_objects[:3], ids=self._object_ids(), scratch=self._objects_scratch,
                             **self._objects_par)
+            if self.scan is not None:
+                ops.range_scan(disp, self._epi_K, self.calib, self.shape, self._d_ground[1], self._d_ground[0],
+                               self._scan_edges, *self._d_scan, ids=None if self.objects is None else self._object_ids(),
+                               scratch=self._scan_scratch, **self._scan_par)
             Ts = None
             if self.motion is not None or self.ego is not None or self.tracks is not None:
                 Ts = self.runner.last.get("Ts")  # None: the frame has no field (first of a sequence) -- roll only
@@ -996,6 +1128,9 @@ class LiveSession:
                 if self.tracks is not None:
                     for host, dev_buf in zip(self._h_tracks[k], self._d_tracks):
                         host.copy_(dev_buf, non_blocking=True)
+                if self.scan is not None:
+                    for host, dev_buf in zip(self._h_scan[k], self._d_scan):
+                        host.copy_(dev_buf, non_blocking=True)
                 self._e_down[k].record(self._s_down)
         self._inflight.append(k)
         self._pushed += 1
@@ -1023,15 +1158,19 @@ class LiveSession:
         if self.objects is not None:
             got = [t.numpy() for t in self._h_objects[k]]  # (objects_from_buffers copies what it keeps)
             out.append(objects_from_buffers(got[0], got[1], got[2], got[3].copy() if self.objects["map"] else None))
+        tracks = None
         if self.tracks is not None:
-            out.append(tracks_from_buffers(*(t.numpy() for t in self._h_tracks[k])))  # (copies what it keeps)
+            tracks = tracks_from_buffers(*(t.numpy() for t in self._h_tracks[k]))  # (copies what it keeps)
+            out.append(tracks)
+        if self.scan is not None:
+            out.append(scan_from_buffers(*(t.numpy() for t in self._h_scan[k]), self._scan_meta, tracks))  # (copies too)
         return out[0] if len(out) == 1 else tuple(out)
 
     def _object_ids(self):
-        """The device id map codd_objects writes: the downloaded one, the tracks' own, or None."""
+        """The device id map codd_objects writes: the downloaded one, the one the tracks and the scan read, or None."""
         if self.objects["map"]:
             return self._d_objects[3]
-        return self._track_ids if self.tracks is not None else None
+        return self._track_ids if self.tracks is not None or self.scan is not None else None
 
     def _ground_bufs(self, bufs):
         """(record, labels, height, grid_count, grid_height) of the buffers present, None for the others."""
@@ -1052,8 +1191,8 @@ class LiveSession:
         """The oldest frame's result: numpy [h,w] (fp32, or uint16 for ``disp_u16``), owned by the caller; with a
         ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None; with ``egomotion``, an ``Ego`` or None
         follows; with ``confidence``, a ``Confidence``; with ``align_to``, an ``Aligned``; with ``epipolar``, an
-        ``Epipolar``; with ``ground``, a ``Ground``; with ``objects``, an ``Objects``; with ``tracks``, a ``Tracks`` comes
-        last."""
+        ``Epipolar``; with ``ground``, a ``Ground``; with ``objects``, an ``Objects``; with ``tracks``, a ``Tracks``; with
+        ``scan``, a ``Scan`` comes last."""
         if self._ready:
             return self._ready.popleft()
         if not self._inflight:
@@ -1087,7 +1226,7 @@ class LiveSession:
                          "_d_ego", "_h_ego", "_ego_scratch", "_d_conf", "_h_conf", "_d_align", "_h_align",
                          "_d_epi", "_h_epi", "_epi_scratch", "_d_ground", "_h_ground", "_ground_scratch",
                          "_d_objects", "_h_objects", "_objects_scratch", "_track_ids", "_d_tracks", "_h_tracks",
-                         "_track_state", "_track_scratch"):
+                         "_track_state", "_track_scratch", "_d_scan", "_h_scan", "_scan_edges", "_scan_scratch"):
                 setattr(self, name, None)
             self._open_done = False
         self._inflight.clear()

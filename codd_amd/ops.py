@@ -7,6 +7,7 @@ import collections
 import ctypes as C
 import functools
 
+import numpy as np
 import torch
 
 from . import _abi
@@ -2269,6 +2270,78 @@ def track_objects(T, depth_prev, K, crop, ids, count, state, trk_count, trk_i, t
                                       state.data_ptr(), state.numel(), scratch.data_ptr(), scratch.numel(),
                                       trk_count.data_ptr(), trk_i.data_ptr(), trk_f.data_ptr(), _stream()), "track_objects")
     return trk_count
+
+
+SCAN_PARAMS = dict(range_min=0.0, range_max=12.8, select=1 << GROUND_OBSTACLE, min_pixels=8)
+SCAN_MAX_BEAMS, SCAN_MAX_BINS, SCAN_MAX_CELLS = 2048, 1024, 2 ** 20  # the limits of codd_range_scan (include/codd_hip.h)
+
+
+def scan_edges(beams, angle_min, angle_max):
+    """The beam-edge table of ``range_scan``: numpy fp32 [beams+1,2] = (sin a_i, cos a_i) with a_i = angle_min + (angle_max -
+    angle_min) * i / beams in float64 (radians from the grid's forward axis, positive to the right), sine and cosine taken
+    in float64 and rounded once.  ValueError outside 1 <= beams <= ``SCAN_MAX_BEAMS`` and -pi/2 <= angle_min < angle_max
+    <= pi/2 (no device call)."""
+    if not (isinstance(beams, (int, np.integer)) and not isinstance(beams, bool) and 1 <= beams <= SCAN_MAX_BEAMS):
+        raise ValueError(f"scan_edges: an integer beams in [1, {SCAN_MAX_BEAMS}] expected, got {beams!r}")
+    lo, hi = float(angle_min), float(angle_max)
+    if not (-np.pi / 2 <= lo < hi <= np.pi / 2):  # (NaN compares false)
+        raise ValueError(f"scan_edges: -pi/2 <= angle_min < angle_max <= pi/2 expected, got {angle_min!r}, {angle_max!r}")
+    a = lo + (hi - lo) * np.arange(int(beams) + 1, dtype=np.float64) / float(beams)
+    return np.stack([np.sin(a), np.cos(a)], 1).astype(np.float32)
+
+
+def range_scan_scratch(beams, bins):
+    """Bytes of scratch ``range_scan`` needs (codd_range_scan_scratch)."""
+    n = int(_abi.load().codd_range_scan_scratch(int(beams), int(bins)))
+    if n <= 0:
+        raise ValueError(f"range_scan_scratch: beams in [1, {SCAN_MAX_BEAMS}], bins in [1, {SCAN_MAX_BINS}] and beams bins <= "
+                         f"2^20 expected, got {beams}, {bins}")
+    return n
+
+
+def range_scan(disp, K, calib, crop, labels, ground_record, edges, count, scan_i, scan_f, ids=None, scratch=None, **par):
+    """How far can I go?  Every floor pixel and every pixel whose label is in the bit set ``select`` (the obstacles) of the
+    ``crop`` (h, w) of the padded disparity ``disp`` [H,W] (or [1,1,H,W]) is projected onto the floor -- the frame of
+    ``objects``' extents -- and binned by bearing, between the beam edges ``edges`` (device fp32 [beams+1,2]: ``scan_edges``),
+    and by range, in ``bins`` = ``par["bins"]`` bins up to ``range_max``; per beam, the nearest bin with at least
+    ``min_pixels`` obstacle pixels is the hit (include/codd_hip.h, codd_range_scan).  ``labels`` and ``ground_record`` are the
+    device tensors ``ground_plane`` wrote, ``K`` and ``calib`` the ones it took; ``ids`` uint16 [h,w] or None: the id map
+    ``objects`` wrote.  Outputs are caller-owned device tensors: ``count`` int32 [4] (hit, clear, unknown beams, obstacle
+    pixels binned); ``scan_f`` fp32 [beams,4] (range: +inf clear, NaN unknown; free range; gx, gz of the hit); ``scan_i``
+    int32 [beams,4] (raster index of the hit pixel, object, obstacle pixels of the hit bin, floor pixels before it; -1 for
+    no pixel / no object).  ``par`` overrides ``SCAN_PARAMS`` and gives ``bins`` (default 128).  ``scratch``: a uint8 tensor
+    of ``range_scan_scratch`` bytes; allocated here when None.  3 launches on the current stream, no host
+    synchronisation."""
+    lib = _abi.load()
+    _require_gpu(disp)
+    unknown = set(par) - set(SCAN_PARAMS) - {"bins"}
+    if unknown:
+        raise TypeError(f"range_scan: unknown parameters {sorted(unknown)}; known: {tuple(SCAN_PARAMS) + ('bins',)}")
+    p = dict(SCAN_PARAMS, bins=128)
+    p.update(par)
+    H, W = disp.shape[-2:]
+    h, w = int(crop[0]), int(crop[1])
+    assert scan_i.dim() == 2, "scan_i: [beams,4] expected"
+    beams, bins = int(scan_i.shape[0]), int(p["bins"])
+    assert disp.dtype == torch.float32 and disp.is_cuda and disp.is_contiguous() and disp.numel() == H * W
+    assert labels.dtype == torch.uint8 and labels.is_cuda and labels.is_contiguous() and tuple(labels.shape) == (h, w)
+    assert ground_record.dtype == torch.float64 and ground_record.is_cuda and ground_record.is_contiguous()
+    assert ground_record.numel() == 32
+    assert edges.dtype == torch.float32 and edges.is_cuda and edges.is_contiguous() and tuple(edges.shape) == (beams + 1, 2)
+    assert count.dtype == torch.int32 and count.is_cuda and count.is_contiguous() and count.numel() == 4
+    assert scan_i.dtype == torch.int32 and scan_i.is_cuda and scan_i.is_contiguous() and tuple(scan_i.shape) == (beams, 4)
+    assert scan_f.dtype == torch.float32 and scan_f.is_cuda and scan_f.is_contiguous() and tuple(scan_f.shape) == (beams, 4)
+    if ids is not None:
+        assert ids.dtype == torch.uint16 and ids.is_cuda and ids.is_contiguous() and tuple(ids.shape) == (h, w)
+    if scratch is None:
+        scratch = torch.empty(range_scan_scratch(beams, bins), dtype=torch.uint8, device=disp.device)
+    assert scratch.dtype == torch.uint8 and scratch.is_cuda and scratch.is_contiguous()
+    _abi.check(lib.codd_range_scan(disp.data_ptr(), H, W, h, w, *[float(v) for v in K], float(calib), labels.data_ptr(),
+                                   ground_record.data_ptr(), None if ids is None else ids.data_ptr(), edges.data_ptr(),
+                                   beams, bins, float(p["range_min"]), float(p["range_max"]), int(p["select"]),
+                                   int(p["min_pixels"]), scratch.data_ptr(), scratch.numel(), count.data_ptr(),
+                                   scan_i.data_ptr(), scan_f.data_ptr(), _stream()), "range_scan")
+    return count
 
 
 ALIGN_MAX_FOOTPRINT = 4  # CODD_ALIGN_MAX_FOOTPRINT of include/codd_hip.h

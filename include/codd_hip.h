@@ -1097,6 +1097,54 @@ int codd_track_objects(const float* T, const float* depth_prev, int H, int W, in
                        long long state_bytes, void* scratch, long long scratch_bytes, int* trk_count, int* trk_i,
                        float* trk_f, void* stream);
 
+/* Live-session range scan (codd_amd/live.py, scan=): for every bearing in front of the camera, how far away the first
+ * obstacle is and how far the floor was seen before it -- a planar laser scan in the frame of codd_objects' extents.  The
+ * reference has no such output; this replaces downloading the label map and the disparity every frame, projecting every
+ * pixel into the ground frame on the host, atan2 and np.minimum.at.  3 launches, no allocation, no host synchronisation, no
+ * launch count or grid that depends on the data, integer atomics only: equal inputs give equal bytes.
+ * disp [H,W], K = (fx, fy, cx, cy), calib, labels [h,w] and ground_record (DEVICE, read on the device) exactly as
+ * codd_objects takes them.  ids uint16 [h,w] (may be NULL): the id map codd_objects wrote.  edges: DEVICE fp32 [beams+1,2] =
+ * (s_i, c_i) = (sin a_i, cos a_i) of the beam edges' angles, measured from the grid's forward axis (gz), positive to the
+ * right (gx), ascending with -pi/2 <= a_0 < a_beams <= pi/2; the entry does not check the table.
+ * Every operation below is one fp32 operation rounded on its own (no fused multiply-add; sqrtf and division correctly
+ * rounded) unless it says fp64.
+ *   per pixel   over the h x w crop.  A pixel TAKES PART iff record[3] != 0 && labels[y,x] < 32 && d = disp[y,x] is finite
+ *               and > 0 and it is a FLOOR pixel (labels[y,x] == CODD_GROUND_FLOOR) or an OBSTACLE pixel ((select >>
+ *               labels[y,x]) & 1; select is codd_objects' bit set and must not contain the floor).  gx, gz: the expressions
+ *               of codd_objects' "per pixel" paragraph, verbatim (r = f x n in fp64, each product and each difference
+ *               rounded on its own, then rounded to fp32): the scan lives in the frame of obj_f's extents bit for bit.  The
+ *               pixel is dropped unless gz > 0 (false for NaN).  rho = sqrtf((gx * gx) + (gz * gz)); dropped unless rho >=
+ *               range_min && rho < range_max.  bin_w = range_max / (float)bins;  k = (int)floorf(rho / bin_w), k == bins
+ *               becomes bins - 1.  side(i) = (c_i * gx) - (s_i * gz) for i = 0 .. beams; cnt = the number of edges with
+ *               side(i) >= 0; the pixel is dropped when cnt == 0 || cnt == beams + 1, otherwise its beam is cnt - 1.  (For a
+ *               table as above and gz > 0 the signs do not increase with i, so the entry finds cnt by bisection.)
+ *   tables      [beam][k], in the scratch, cleared on every call: O the obstacle pixels, F the floor pixels (int32 sums);
+ *               N the minimum over the obstacle pixels of ((uint64)bits(rho) << 32) | (y * w + x): the nearest pixel, ties to
+ *               the smallest raster index (rho > 0: its bits order as it does).
+ *   per beam    kh = the smallest k with O[k] >= min_pixels: the HIT bin (nearer bins with fewer pixels do not stop the
+ *               beam); limit = kh, or bins without a hit; kf = the largest k < limit with F[k] >= min_pixels; free =
+ *               (float)(kf + 1) * bin_w, or 0 without one; floor = the sum of F[k] over k < limit.
+ *   outputs     caller-owned device buffers, every row rewritten on every call.  scan_f fp32 [beams,4], scan_i int32
+ *               [beams,4]:  a HIT beam: (rho of N[kh], free, gx, gz) and (index of N[kh], object, O[kh], floor), gx and gz
+ *               recomputed from the hit pixel by the expressions above, object = ids[index], or -1 when ids == NULL or the
+ *               value is 0xFFFF;  no hit and free > 0, a CLEAR beam (clear as far as the floor was seen): (+inf, free, 0,
+ *               0) and (-1, -1, 0, floor);  neither, an UNKNOWN beam: (NaN with the bits 0x7fc00000, 0, 0, 0) and (-1, -1, 0,
+ *               floor).  scan_count int32 [4]: (hit beams, clear beams, unknown beams, the sum of all O).  With record[3]
+ *               == 0 every beam is unknown and scan_count = (0, 0, beams, 0).
+ * scratch: codd_range_scan_scratch(beams, bins) bytes (-1 for beams outside [1, 2048], bins outside [1, 1024] or beams bins
+ * > 2^20), 16 per (beam, bin) plus the alignment, contents irrelevant, any alignment.  No pointer needs more than its
+ * element's alignment.
+ * CODD_EINVAL, before any launch: disp, labels, ground_record, edges, scratch, scan_count, scan_i or scan_f NULL; a
+ * non-positive size, h > H, w > W or h w >= 2^31; beams, bins outside the limits above; fx, fy, calib or range_max not
+ * finite and > 0; cx or cy not finite; range_min negative, NaN or >= range_max; select 0 or with the bit of
+ * CODD_GROUND_FLOOR; min_pixels < 1; scratch_bytes below the size function's answer. */
+long long codd_range_scan_scratch(int beams, int bins);
+int codd_range_scan(const float* disp, int H, int W, int h, int w, float fx, float fy, float cx, float cy, float calib,
+                    const unsigned char* labels, const double* ground_record, const unsigned short* ids,
+                    const float* edges, int beams, int bins, float range_min, float range_max, unsigned select,
+                    int min_pixels, void* scratch, long long scratch_bytes, int* scan_count, int* scan_i, float* scan_f,
+                    void* stream);
+
 /* Ablation plug-ins.  codd_fusion_select: mode 0 = KalmanFusion (model/fusion/others.py:124-153; constant
  * gain K = Q/(Q+R), the reference never updates P), mode 1 = GTFusion (:54-86; gt [B,1,hg,wg], zero-padded).
  * cur, warp, out: [B,1,H,W]. */
