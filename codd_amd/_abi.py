@@ -159,6 +159,9 @@ SIGNATURES = {
     "codd_range_scan_scratch": (_ll, [_i, _i]),
     "codd_range_scan": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _p, _i, _i, _f, _f, C.c_uint, _i, _p, _ll, _p, _p,
                              _p, _p]),
+    "codd_local_map_scratch": (_ll, [_i, _i]),
+    "codd_local_map": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _i, _i, _i, _f, _f, _f, C.c_uint, _i, _i, _i, _i, _i,
+                            _i, _i, _i, _i, _p, _p, _p, _p, _ll, _p, _p, _p, _p]),
     "codd_align_depth": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, C.POINTER(AlignView), _i, _i, _i, _p, _p, _p]),
 }
 

@@ -21,6 +21,8 @@
 
 #pragma clang fp contract(off)  // every operation of the contract rounds once
 
+#include "floor_frame.h"  // ScanFrame, scan_frame, scan_ground: the ground frame of codd_objects' "per pixel" paragraph
+
 #define SCAN_BW 8   // a wave's block: SCAN_BW x SCAN_BW pixels
 #define SCAN_TW 32  // a workgroup's tile: four blocks side by side
 #define SCAN_MAX_BEAMS 2048
@@ -43,27 +45,6 @@ struct ScanArgs {
   int W, h, w, beams, bins, min_pixels;
   float fx, fy, cx, cy, calib, range_min, range_max, bin_w;
 };
-
-// the ground frame of codd_objects' "per pixel" paragraph
-struct ScanFrame {
-  float r0, r1, r2, f0, f1, f2;
-};
-
-__device__ __forceinline__ ScanFrame scan_frame(const double* rec) {
-  const double nx = rec[8], ny = rec[9], nz = rec[10], f0d = rec[22], f1d = rec[23], f2d = rec[24];
-  ScanFrame g;
-  g.r0 = (float)(f1d * nz - f2d * ny); g.r1 = (float)(f2d * nx - f0d * nz); g.r2 = (float)(f0d * ny - f1d * nx);
-  g.f0 = (float)f0d; g.f1 = (float)f1d; g.f2 = (float)f2d;
-  return g;
-}
-
-__device__ __forceinline__ void scan_ground(const ScanArgs& a, const ScanFrame& g, int y, int x, float d, float* gx, float* gz) {
-  const float p0 = (float)x - a.cx, p1 = (float)y - a.cy;
-  const float Z = a.calib / d;
-  const float X0 = Z * (p0 / a.fx), X1 = Z * (p1 / a.fy);
-  *gx = (g.r0 * X0 + g.r1 * X1) + g.r2 * Z;
-  *gz = (g.f0 * X0 + g.f1 * X1) + g.f2 * Z;
-}
 
 // ---- 1: clear
 __global__ __launch_bounds__(256) void scan_clear_kernel(ScanArgs a) {

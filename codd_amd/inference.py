@@ -95,6 +95,12 @@ def parse_args(argv=None):
                         "beams] (range +inf: clear as far as the floor was seen, NaN: unknown; object -1: none, or no "
                         "--objects), hits, clear, unknown and obstacle_pixels [1, frames], angle_min, angle_increment "
                         "(radians), range_min and range_max")
+    p.add_argument("--localmap", action="store_true",
+                   help="--ground --ego: a rolling occupancy map around the camera, kept across the frames; also write "
+                        "<name>.localmap.pred.npz: logodds int16 and age uint8 [1, frames, gh, gw] (age 255: never seen), pose "
+                        "float64 [1, frames, 4] (x, z and the unit heading in the map), origin int64 [1, frames, 2] (the world "
+                        "cell of [0,0]), integrated, linked, restarts, occupied, free and unknown int32 [1, frames], cell, "
+                        "occ_level and free_level")
     p.add_argument("--align-footprint", type=int, default=None, choices=[1, 2, 3, 4],
                    help="--align: target pixels per source pixel and axis (default: the smallest that leaves no hole lines)")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
@@ -154,6 +160,8 @@ def parse_args(argv=None):
         p.error("--tracks needs --objects")
     if args.scan and not args.ground:
         p.error("--scan needs --ground")
+    if args.localmap and not (args.ground and args.ego):
+        p.error("--localmap needs --ground and --ego")
     if args.ground_grid is not None:
         m = re.fullmatch(r"(\d+)x(\d+)", args.ground_grid)
         if not m or not int(m.group(1)) or not int(m.group(2)):
@@ -329,7 +337,8 @@ def run_live(args, model, videos):
     <name>.objects.pred.npz (per-frame n, found and the object tables padded to max_objects, written with or without
     --show; the id maps with --show only) and, with --tracks, <name>.tracks.pred.npz (per-frame n, continued, started, ended
     and the track tables padded to max_objects, written with or without --show) and, with --scan, <name>.scan.pred.npz
-    (per-frame ranges, free ranges, objects and counts, written with or without --show).  With --pixel-format the
+    (per-frame ranges, free ranges, objects and counts, written with or without --show) and, with --localmap,
+    <name>.localmap.pred.npz (per-frame map, age plane, pose and counts, written with or without --show).  With --pixel-format the
     frame files are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU.  With
     --calibration the frames (files or --frame-size) have the calibration's source size and every result has --net-size."""
     from PIL import Image
@@ -359,6 +368,8 @@ def run_live(args, model, videos):
         extra["tracks"] = True
     if getattr(args, "scan", False):
         extra["scan"] = True
+    if getattr(args, "localmap", False):
+        extra["localmap"] = True
     raw = getattr(args, "pixel_format", None)
     if raw:
         extra.update(pixel_format=raw, pitch=args.pitch, yuv=args.yuv or "bt601")
@@ -398,11 +409,14 @@ def run_live(args, model, videos):
             if align_to:
                 aligned = _NpzStream(osp.join(args.show_dir, name + ".aligned.pred.npz"), "depth",
                                      (1, nf) + s.align_target.camera.size, np.float32)
-        n, epis, grounds, objs, trks, scans = 0, [], [], [], [], []
+        n, epis, grounds, objs, trks, scans, maps = 0, [], [], [], [], [], []
         try:
             frames = iter_raw_frames(lefts, rights, raw, src, args.pitch) if raw else iter_frames(lefts, rights)
             for res in live_results(s, frames):
                 n += 1
+                if "localmap" in extra:
+                    res, lm = res[:-1], res[-1]  # (an Ego and a Ground precede it: still a tuple)
+                    maps.append(lm)
                 if "scan" in extra:
                     res, sc = res[:-1], res[-1]  # (a Ground precedes it: still a tuple)
                     scans.append(sc)
@@ -530,6 +544,20 @@ def run_live(args, model, videos):
             print(f"{name}: scan: {beams} beams; {sum(sc.hits for sc in scans)} hits, {sum(sc.clear for sc in scans)} clear, "
                   f"{sum(sc.unknown for sc in scans)} unknown in {len(scans)} frames"
                   + (f", nearest hit {min(near):.3f}" if near else ""))
+        if "localmap" in extra:
+            os.makedirs(args.show_dir, exist_ok=True)
+            np.savez(osp.join(args.show_dir, name + ".localmap.pred.npz"),
+                     logodds=np.array([[lm.logodds for lm in maps]], np.int16), age=np.array([[lm.age for lm in maps]], np.uint8),
+                     pose=np.array([[lm.pose[:2] + lm.pose[2] for lm in maps]], np.float64).reshape(1, len(maps), 4),
+                     origin=np.array([[lm.origin for lm in maps]], np.int64).reshape(1, len(maps), 2),
+                     **{k: np.array([[int(getattr(lm, k)) for lm in maps]], np.int32)
+                        for k in ("integrated", "linked", "restarts", "occupied", "free", "unknown")},
+                     cell=np.array(s.localmap["cell"], np.float64), occ_level=np.array(s.localmap["occ_level"], np.int32),
+                     free_level=np.array(s.localmap["free_level"], np.int32))
+            gh, gw = s.localmap["grid"]
+            print(f"{name}: localmap: {gh} x {gw} cells; {sum(lm.integrated for lm in maps)} integrated, "
+                  f"{sum(lm.linked for lm in maps)} linked in {len(maps)} frames, {maps[-1].restarts if maps else 0} restarts"
+                  + (f", {maps[-1].occupied} occupied and {maps[-1].free} free cells at the end" if maps else ""))
         print(f"{name}: {n} frames")
     for s in sessions.values():
         s.close()

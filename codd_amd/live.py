@@ -69,6 +69,11 @@ With ``scan=`` (which needs ``ground=``) the session says how far one can go in 
 labels, record and id map, bins the floor and obstacle pixels by bearing and range in the frame of the objects' extents,
 and returns a planar laser scan -- per beam the range of the first obstacle, the pixel and the object that made it, and
 how far the floor was seen in front of it.
+
+With ``localmap=`` (which needs ``ground=`` and ``egomotion=``) the session keeps a map across frames: ``codd_local_map``
+runs after ``codd_ground_plane`` and ``codd_ego_motion`` on their device records and labels, advances the camera's planar
+pose by the ego fit levelled with each frame's own floor normal, and adds the frame's floor and obstacle pixels to a rolling
+occupancy grid of integer log-odds that follows the camera.  The map, its age plane and the pose state stay on the device.
 """
 from collections import deque, namedtuple
 
@@ -95,6 +100,10 @@ OBJECT_DEFAULTS = dict(select=("obstacle",), gap_px=1.0, gap_rel=0.05, min_pixel
                        map=False)
 TRACK_DEFAULTS = dict(min_votes=16)
 SCAN_DEFAULTS = dict(beams=256, angles_deg=None, range_min=0.0, range_max=12.8, bins=128, select=("obstacle",), min_pixels=8)
+# The increments and levels of ops.MAP_PARAMS are chosen by reasoning, not measured on real footage (see there).
+LOCALMAP_DEFAULTS = dict(grid=(128, 128), cell=0.1, range_min=0.0, range_max=12.8, select=("obstacle",), min_pixels=4, l_occ=4,
+                         l_free=2, l_min=-32, l_max=64, decay=0, occ_level=8, free_level=-4, lost="reset")
+LOCALMAP_LOST = dict(reset=ops.MAP_RESET, hold=ops.MAP_HOLD)
 OBJECT_LABELS = dict(floor=ops.GROUND_FLOOR, obstacle=ops.GROUND_OBSTACLE, overhead=ops.GROUND_OVERHEAD,
                      below=ops.GROUND_BELOW)  # the names ``select`` takes
 
@@ -231,6 +240,46 @@ def scan_from_buffers(count, scan_i, scan_f, edges_meta, tracks=None):
     a0, da, r0, r1 = (float(v) for v in edges_meta)
     return Scan(a0, da, r0, r1, sf[:, 0].copy(), sf[:, 1].copy(), sf[:, 2:4].copy(), si[:, 0].copy(), obj, track,
                 si[:, 2].copy(), si[:, 3].copy(), int(count[0]), int(count[1]), int(count[2]), int(count[3]))
+
+
+# One frame's view of the rolling occupancy map, caller-owned.  logodds int16 [gh,gw] and age uint8 [gh,gw]: the window
+# unrolled, [j,i] = world cell (origin[0] + i, origin[1] + j) of the map frame -- the floor frame of the first integrated
+# frame, x to its right, z forward, cells of ``cell`` units (the unit of calib / fx); age 255: never observed inside the
+# window, otherwise frames since the last observation (254: that or more).  pose = (x, z, (hx, hz)): the camera's foot point
+# and unit heading in the map; origin = (ix0, iz0); integrated: the frame had a floor and its pixels were added; linked: the
+# pose was advanced by the ego fit (False on the first frame of a sequence and on a LOST one); restarts; frames since the
+# last reset; occupied, free and unknown: cells with logodds >= occ_level, <= free_level and with age 255; pixels: the
+# pixels added; step = (dx, dz): the camera's planar step in its previous floor frame; occ_level and free_level as given.
+_LocalMap = namedtuple("LocalMap", "logodds age pose origin cell integrated linked restarts frames occupied free unknown pixels "
+                                   "step occ_level free_level")
+MAP_FREE, MAP_OCCUPIED, MAP_UNKNOWN = 0, 1, 2  # the values of LocalMap.state()
+
+
+class LocalMap(_LocalMap):
+    __slots__ = ()
+
+    def state(self):
+        """uint8 [gh,gw]: ``MAP_OCCUPIED`` where logodds >= occ_level, ``MAP_FREE`` where logodds <= free_level (and not
+        occupied), ``MAP_UNKNOWN`` elsewhere."""
+        out = np.full(self.logodds.shape, MAP_UNKNOWN, np.uint8)
+        out[self.logodds <= self.free_level] = MAP_FREE
+        out[self.logodds >= self.occ_level] = MAP_OCCUPIED
+        return out
+
+    def world_xz(self, j, i):
+        """The centre (x, z) of cell [j,i] in the map frame (float64; arrays broadcast)."""
+        j, i = np.broadcast_arrays(np.asarray(j, np.float64), np.asarray(i, np.float64))
+        x, z = (self.origin[0] + i + 0.5) * self.cell, (self.origin[1] + j + 0.5) * self.cell
+        return (float(x), float(z)) if x.ndim == 0 else (x, z)
+
+
+def localmap_from_buffers(record, map_out, age_out, cell, occ_level, free_level):
+    """record float64 [16], map_out int16 [gh,gw] and age_out uint8 [gh,gw] of codd_local_map (include/codd_hip.h) ->
+    ``LocalMap`` (copies: the buffers may be reused)."""
+    r = np.asarray(record, np.float64)
+    return LocalMap(np.array(map_out, np.int16), np.array(age_out, np.uint8), (float(r[4]), float(r[5]), (float(r[6]), float(r[7]))),
+                    (int(r[8]), int(r[9])), float(cell), bool(r[0] != 0), bool(r[1] != 0), int(r[2]), int(r[3]), int(r[11]),
+                    int(r[12]), int(r[13]), int(r[10]), (float(r[14]), float(r[15])), int(occ_level), int(free_level))
 
 
 def _unit_up(up, pitch_deg=0.0):
@@ -577,6 +626,63 @@ def _check_scan(scan, ground=True):
     return p
 
 
+def _check_localmap(localmap, ground=True, egomotion=True):
+    """False / None -> None; True -> the defaults; a dict overrides them.  ValueError otherwise, and for ``localmap``
+    without ``ground`` or without ``egomotion`` (no device call)."""
+    if localmap is None or localmap is False:
+        return None
+    if not (localmap is True or isinstance(localmap, dict)):
+        raise ValueError(f"localmap: False, True or a dict of {tuple(LOCALMAP_DEFAULTS)} expected, got {localmap!r}")
+    if ground is None or ground is False:
+        raise ValueError("localmap: needs ground= (the map is built from the ground stage's labels, in its floor frame)")
+    if egomotion is None or egomotion is False:
+        raise ValueError("localmap: needs egomotion= (the pose is advanced by the ego stage's fit)")
+    if localmap is True:
+        return dict(LOCALMAP_DEFAULTS)
+    unknown = set(localmap) - set(LOCALMAP_DEFAULTS)
+    if unknown:
+        raise ValueError(f"localmap: unknown keys {sorted(unknown)}; known: {tuple(LOCALMAP_DEFAULTS)}")
+    p = dict(LOCALMAP_DEFAULTS, **localmap)
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)  # noqa: E731
+    g = p["grid"]
+    if not (isinstance(g, (tuple, list)) and len(g) == 2 and all(is_int(v) and 1 <= v <= ops.MAP_MAX_SIDE for v in g)
+            and g[0] * g[1] <= ops.MAP_MAX_CELLS):
+        raise ValueError(f"localmap: grid = (gh, gw), integers in [1, {ops.MAP_MAX_SIDE}] with gh gw <= {ops.MAP_MAX_CELLS} "
+                         f"expected, got {g!r}")
+    p["grid"] = (int(g[0]), int(g[1]))
+    for k in ("cell", "range_min", "range_max"):
+        try:
+            p[k] = float(p[k])
+        except (TypeError, ValueError):
+            raise ValueError(f"localmap: a number expected for {k}, got {p[k]!r}") from None
+        if not np.isfinite(p[k]):
+            raise ValueError(f"localmap: a finite {k} expected, got {p[k]!r}")
+    if not p["cell"] > 0:
+        raise ValueError(f"localmap: positive cell expected, got {p['cell']!r}")
+    if not p["range_max"] > 0:
+        raise ValueError(f"localmap: positive range_max expected, got {p['range_max']!r}")
+    if not 0 <= p["range_min"] < p["range_max"]:
+        raise ValueError(f"localmap: 0 <= range_min < range_max expected, got {p['range_min']!r}, {p['range_max']!r}")
+    for k, lo_, hi_ in (("min_pixels", 1, 2 ** 31 - 1), ("l_occ", 0, 32767), ("l_free", 0, 32767), ("decay", 0, 32767),
+                        ("l_min", -32768, 0), ("l_max", 0, 32767), ("occ_level", -32768, 32767), ("free_level", -32768, 32767)):
+        if not (is_int(p[k]) and lo_ <= p[k] <= hi_):
+            raise ValueError(f"localmap: an integer {k} in [{lo_}, {hi_}] expected, got {p[k]!r}")
+        p[k] = int(p[k])
+    if not p["free_level"] < p["occ_level"]:
+        raise ValueError(f"localmap: free_level < occ_level expected, got {p['free_level']!r}, {p['occ_level']!r}")
+    sel = p["select"]
+    if isinstance(sel, str):
+        sel = (sel,)
+    if not (isinstance(sel, (tuple, list)) and all(isinstance(v, str) and v in OBJECT_LABELS for v in sel)):
+        raise ValueError(f"localmap: select: names of {tuple(OBJECT_LABELS)} expected, got {p['select']!r}")
+    if "floor" in sel:
+        raise ValueError("localmap: select: the floor is the free evidence, not an obstacle")
+    p["select"] = tuple(sel)
+    if not (isinstance(p["lost"], str) and p["lost"] in LOCALMAP_LOST):
+        raise ValueError(f"localmap: lost: one of {tuple(LOCALMAP_LOST)} expected, got {p['lost']!r}")
+    return p
+
+
 def scan_span(p, K, w):
     """(angle_min, angle_max) in radians of the checked ``scan`` dict: ``angles_deg``, or the camera's own horizontal field
     atan((0 - cx) / fx) .. atan((w - 1 - cx) / fx)."""
@@ -721,8 +827,8 @@ class LiveSession:
 
     ``egomotion`` (False, True, or a dict overriding ``iters``, ``delta_px``, ``tau_px``, ``min_valid``): ``pop`` and
     ``step`` also return an ``Ego`` (or None for a frame without a field).  The tuple order is fixed:
-    ``result[, motion][, ego][, confidence][, aligned][, epipolar][, ground][, objects][, tracks][, scan]``, each part
-    present iff requested.
+    ``result[, motion][, ego][, confidence][, aligned][, epipolar][, ground][, objects][, tracks][, scan][, localmap]``,
+    each part present iff requested.
 
     ``confidence`` (False, True, or a dict overriding ``occ_px`` (1.0 pixel) and ``tau`` (24.0 grey levels)): ``pop`` and
     ``step`` also return a ``Confidence(flags, residual)`` on the CURRENT frame's grid, for every frame (never None).  It
@@ -807,12 +913,25 @@ class LiveSession:
     is the range of its nearest pixel; ``free`` says how far floor was seen in front of it.  With ``objects`` the hit names
     its object, with ``tracks`` its track.  A frame without a floor has only unknown beams.  Defined in include/codd_hip.h
     (codd_range_scan).
+
+    ``localmap`` (False, True, or a dict overriding ``LOCALMAP_DEFAULTS``; needs ``ground`` and ``egomotion``, ValueError
+    without either): ``pop`` and ``step`` also return a ``LocalMap``, for every frame (never None), last in the tuple: a
+    rolling occupancy map of ``grid`` = (gh, gw) cells of ``cell`` units, centred on the camera's cell and moving by whole
+    cells, in the floor frame of the first integrated frame (it never rotates).  The pose advances by the ego stage's fit,
+    levelled by each frame's own floor normal.  Every floor pixel and every pixel labelled one of ``select`` with a range
+    in [``range_min``, ``range_max``) on the floor falls into a cell; a cell with ``min_pixels`` obstacle pixels gains
+    ``l_occ`` (up to ``l_max``), else one with ``min_pixels`` floor pixels loses ``l_free`` (down to ``l_min``), every
+    other cell ages and moves ``decay`` towards 0.  ``occ_level`` and ``free_level`` are the levels of
+    ``LocalMap.state()`` and of the counts.  ``lost`` says what a frame does whose pose cannot be advanced (no field, an
+    ego fit that failed): ``"reset"`` starts a new map there, ``"hold"`` keeps map and pose as if the camera stood still.
+    The first frame of a sequence starts a new map.  The defaults are reasoned, not measured on real footage.  Moving
+    things are not excluded; free evidence and ``decay`` erase them.  Defined in include/codd_hip.h (codd_local_map).
     """
 
     def __init__(self, estimator, shape, intrinsics=None, calib=None, output="depth",
                  bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False,
                  pixel_format="rgb8", yuv="bt601", pitch=None, calibration=None, zoom=1.0, align_to=None, align=None,
-                 epipolar=False, ground=False, objects=False, tracks=False, scan=False):
+                 epipolar=False, ground=False, objects=False, tracks=False, scan=False, localmap=False):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
@@ -828,6 +947,7 @@ class LiveSession:
         self.objects = _check_objects(objects, self.ground)
         self.tracks = _check_tracks(tracks, self.objects, estimator)
         self.scan = _check_scan(scan, self.ground)
+        self.localmap = _check_localmap(localmap, self.ground, self.ego)
         h, w = int(shape[0]), int(shape[1])
         if h <= 0 or w <= 0:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
@@ -874,6 +994,10 @@ class LiveSession:
             self._scan_meta = (lo, (hi - lo) / sc["beams"], sc["range_min"], sc["range_max"])
             self._scan_par = dict(range_min=sc["range_min"], range_max=sc["range_max"], bins=sc["bins"],
                                   select=select_mask(sc["select"]), min_pixels=sc["min_pixels"])
+        if self.localmap is not None:
+            lm = self.localmap
+            self._map_par = dict({k: lm[k] for k in ops.MAP_PARAMS if k not in ("select", "lost")},
+                                 select=select_mask(lm["select"]), lost=LOCALMAP_LOST[lm["lost"]])
         self.src_shape = (h, w) if self.rect is None else self.rect.size  # the size of a frame as the camera hands it out
         # (rows, row_bytes, pitch, nbytes) of a source frame; ValueError if invalid
         self._layout = frame_layout(pixel_format, self.src_shape[0], self.src_shape[1], pitch)
@@ -896,6 +1020,7 @@ class LiveSession:
         self._open_done = False
         self._pushed = 0
         self._track_fresh = True  # the next frame is the first of a sequence for the tracks' state
+        self._map_fresh = True  # and for the local map's
         self._inflight = deque()  # slots, oldest first
         self._ready = deque()  # results popped on the caller's behalf by a push that found the pipeline full
 
@@ -995,6 +1120,15 @@ class LiveSession:
                                 for _ in range(DEPTH)]
                 self._scan_edges = torch.from_numpy(self._scan_edges_host).to(dev)
                 self._scan_scratch = torch.empty(ops.range_scan_scratch(beams, self.scan["bins"]), dtype=torch.uint8, device=dev)
+            if self.localmap is not None:
+                gh, gw = self.localmap["grid"]
+                self._d_map = [torch.zeros(16, dtype=torch.float64, device=dev), torch.zeros(gh, gw, dtype=torch.int16, device=dev),
+                               torch.zeros(gh, gw, dtype=torch.uint8, device=dev)]  # record, map_out, age_out
+                self._h_map = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_map]
+                               for _ in range(DEPTH)]
+                self._map_state = [torch.zeros(32, dtype=torch.float64, device=dev), torch.zeros(gh, gw, dtype=torch.int16, device=dev),
+                                   torch.full((gh, gw), 255, dtype=torch.uint8, device=dev)]  # state, logodds, age
+                self._map_scratch = torch.empty(ops.local_map_scratch(gh, gw), dtype=torch.uint8, device=dev)
             self._s_up, self._s_down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             ev = lambda: [torch.cuda.Event() for _ in range(DEPTH)]  # noqa: E731
             self._e_up, self._e_ingest, self._e_export, self._e_down = ev(), ev(), ev(), ev()
@@ -1086,6 +1220,11 @@ class LiveSession:
                     ops.ego_motion(Ts, self._depth_prev, self._K, self.shape, rec, mov, res, scale=self.calib / self._bf,
                                    scratch=self._ego_scratch, **self.ego)
                 self._has_ego[k] = Ts is not None
+            if self.localmap is not None:  # (after the ground stage and the ego fit whose records it reads on the device)
+                ops.local_map(disp, self._epi_K, self.calib, self.shape, self._d_ground[1], self._d_ground[0],
+                              self._d_ego[0] if Ts is not None else None, *self._map_state, self._d_map[1], self._d_map[2],
+                              self._d_map[0], fresh=self._map_fresh, scratch=self._map_scratch, **self._map_par)
+                self._map_fresh = False
             if self.tracks is not None:  # (after the ego fit it reads, before export_motion rolls the depth map)
                 with_ego = self.ego is not None and Ts is not None
                 ops.track_objects(Ts, self._depth_prev, self._K, self.shape, self._object_ids(), self._d_objects[0],
@@ -1131,6 +1270,9 @@ class LiveSession:
                 if self.scan is not None:
                     for host, dev_buf in zip(self._h_scan[k], self._d_scan):
                         host.copy_(dev_buf, non_blocking=True)
+                if self.localmap is not None:
+                    for host, dev_buf in zip(self._h_map[k], self._d_map):
+                        host.copy_(dev_buf, non_blocking=True)
                 self._e_down[k].record(self._s_down)
         self._inflight.append(k)
         self._pushed += 1
@@ -1164,6 +1306,9 @@ class LiveSession:
             out.append(tracks)
         if self.scan is not None:
             out.append(scan_from_buffers(*(t.numpy() for t in self._h_scan[k]), self._scan_meta, tracks))  # (copies too)
+        if self.localmap is not None:
+            lm = self.localmap
+            out.append(localmap_from_buffers(*(t.numpy() for t in self._h_map[k]), lm["cell"], lm["occ_level"], lm["free_level"]))
         return out[0] if len(out) == 1 else tuple(out)
 
     def _object_ids(self):
@@ -1192,7 +1337,7 @@ class LiveSession:
         ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None; with ``egomotion``, an ``Ego`` or None
         follows; with ``confidence``, a ``Confidence``; with ``align_to``, an ``Aligned``; with ``epipolar``, an
         ``Epipolar``; with ``ground``, a ``Ground``; with ``objects``, an ``Objects``; with ``tracks``, a ``Tracks``; with
-        ``scan``, a ``Scan`` comes last."""
+        ``scan``, a ``Scan``; with ``localmap``, a ``LocalMap`` comes last."""
         if self._ready:
             return self._ready.popleft()
         if not self._inflight:
@@ -1216,6 +1361,7 @@ class LiveSession:
         self.runner.reset()
         self.est.reset_inference_state()
         self._track_fresh = True
+        self._map_fresh = True
 
     def close(self):
         if self._open_done:
@@ -1226,7 +1372,8 @@ class LiveSession:
                          "_d_ego", "_h_ego", "_ego_scratch", "_d_conf", "_h_conf", "_d_align", "_h_align",
                          "_d_epi", "_h_epi", "_epi_scratch", "_d_ground", "_h_ground", "_ground_scratch",
                          "_d_objects", "_h_objects", "_objects_scratch", "_track_ids", "_d_tracks", "_h_tracks",
-                         "_track_state", "_track_scratch", "_d_scan", "_h_scan", "_scan_edges", "_scan_scratch"):
+                         "_track_state", "_track_scratch", "_d_scan", "_h_scan", "_scan_edges", "_scan_scratch",
+                         "_d_map", "_h_map", "_map_state", "_map_scratch"):
                 setattr(self, name, None)
             self._open_done = False
         self._inflight.clear()

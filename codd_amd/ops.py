@@ -2344,6 +2344,68 @@ def range_scan(disp, K, calib, crop, labels, ground_record, edges, count, scan_i
     return count
 
 
+MAP_RESET, MAP_HOLD = 0, 1  # CODD_MAP_RESET, CODD_MAP_HOLD of include/codd_hip.h
+MAP_MAX_SIDE, MAP_MAX_CELLS = 4096, 2 ** 22  # the limits of codd_local_map
+# The increments and levels are chosen by reasoning, not measured on real footage: an occupied observation weighs twice a
+# free one (a missed obstacle costs more than a detour); two occupied observations make a cell occupied, so one frame of
+# stereo speckle does not; two free ones make it free; the clamps bound how long stale evidence outlives the scene (a cell
+# saturated at 64 takes 34 free frames to count as free, one saturated at -32 ten occupied frames to count as occupied).
+MAP_PARAMS = dict(cell=0.1, range_min=0.0, range_max=12.8, select=1 << GROUND_OBSTACLE, min_pixels=4, l_occ=4, l_free=2,
+                  l_min=-32, l_max=64, decay=0, occ_level=8, free_level=-4, lost=MAP_RESET)
+
+
+def local_map_scratch(gh, gw):
+    """Bytes of scratch ``local_map`` needs (codd_local_map_scratch)."""
+    n = int(_abi.load().codd_local_map_scratch(int(gh), int(gw)))
+    if n <= 0:
+        raise ValueError(f"local_map_scratch: gh, gw in [1, {MAP_MAX_SIDE}] and gh gw <= 2^22 expected, got {gh}, {gw}")
+    return n
+
+
+def local_map(disp, K, calib, crop, labels, ground_record, ego_record, state, logodds, age, map_out, age_out, record, fresh=False,
+              scratch=None, **par):
+    """What is around me, and what was?  One frame into the rolling occupancy map (include/codd_hip.h, codd_local_map).
+    ``disp`` [H,W] (or [1,1,H,W]), ``K``, ``calib``, ``crop`` (h, w), ``labels`` and ``ground_record`` as ``objects`` takes
+    them; ``ego_record``: the device fp32 [16] ``ego_motion`` wrote for this frame, or None for a frame without a field;
+    ``fresh``: the first frame of a sequence.  Persistent, caller-owned device tensors, zeroed once and then left to this
+    call: ``state`` float64 [32], ``logodds`` int16 [gh,gw] and ``age`` uint8 [gh,gw] (toroidal storage).  Outputs,
+    caller-owned device tensors: ``map_out`` int16 [gh,gw] and ``age_out`` uint8 [gh,gw] (the unrolled window, [j,i] = world
+    cell (ix0 + i, iz0 + j)) and ``record`` float64 [16].  ``par`` overrides ``MAP_PARAMS``.  ``scratch``: a uint8 tensor of
+    ``local_map_scratch`` bytes; allocated here when None.  4 launches on the current stream, no host synchronisation."""
+    lib = _abi.load()
+    _require_gpu(disp)
+    unknown = set(par) - set(MAP_PARAMS)
+    if unknown:
+        raise TypeError(f"local_map: unknown parameters {sorted(unknown)}; known: {tuple(MAP_PARAMS)}")
+    p = dict(MAP_PARAMS)
+    p.update(par)
+    H, W = disp.shape[-2:]
+    h, w = int(crop[0]), int(crop[1])
+    assert logodds.dim() == 2, "logodds: [gh,gw] expected"
+    gh, gw = int(logodds.shape[0]), int(logodds.shape[1])
+    assert disp.dtype == torch.float32 and disp.is_cuda and disp.is_contiguous() and disp.numel() == H * W
+    assert labels.dtype == torch.uint8 and labels.is_cuda and labels.is_contiguous() and tuple(labels.shape) == (h, w)
+    assert ground_record.dtype == torch.float64 and ground_record.is_cuda and ground_record.is_contiguous()
+    assert ground_record.numel() == 32
+    if ego_record is not None:
+        assert ego_record.dtype == torch.float32 and ego_record.is_cuda and ego_record.is_contiguous() and ego_record.numel() == 16
+    assert state.dtype == torch.float64 and state.is_cuda and state.is_contiguous() and state.numel() == 32
+    assert record.dtype == torch.float64 and record.is_cuda and record.is_contiguous() and record.numel() == 16
+    for t, dt in ((logodds, torch.int16), (map_out, torch.int16), (age, torch.uint8), (age_out, torch.uint8)):
+        assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (gh, gw)
+    if scratch is None:
+        scratch = torch.empty(local_map_scratch(gh, gw), dtype=torch.uint8, device=disp.device)
+    assert scratch.dtype == torch.uint8 and scratch.is_cuda and scratch.is_contiguous()
+    _abi.check(lib.codd_local_map(disp.data_ptr(), H, W, h, w, *[float(v) for v in K], float(calib), labels.data_ptr(),
+                                  ground_record.data_ptr(), None if ego_record is None else ego_record.data_ptr(),
+                                  1 if fresh else 0, gh, gw, float(p["cell"]), float(p["range_min"]), float(p["range_max"]),
+                                  int(p["select"]), int(p["min_pixels"]), int(p["l_occ"]), int(p["l_free"]), int(p["l_min"]),
+                                  int(p["l_max"]), int(p["decay"]), int(p["occ_level"]), int(p["free_level"]), int(p["lost"]),
+                                  state.data_ptr(), logodds.data_ptr(), age.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                  map_out.data_ptr(), age_out.data_ptr(), record.data_ptr(), _stream()), "local_map")
+    return record
+
+
 ALIGN_MAX_FOOTPRINT = 4  # CODD_ALIGN_MAX_FOOTPRINT of include/codd_hip.h
 
 

@@ -1145,6 +1145,90 @@ int codd_range_scan(const float* disp, int H, int W, int h, int w, float fx, flo
                     int min_pixels, void* scratch, long long scratch_bytes, int* scan_count, int* scan_i, float* scan_f,
                     void* stream);
 
+/* Live-session local map (codd_amd/live.py, localmap=): a rolling occupancy map with integer log-odds in a fixed
+ * floor-aligned frame that follows the camera.  codd_ground_plane and codd_range_scan describe one frame; this entry joins
+ * the frames: codd_ego_motion's record says how the camera moved, codd_ground_plane's record and labels where the floor is
+ * and which pixels stand on it.  The reference has no such output; this replaces downloading the labels and the disparity
+ * every frame, composing the poses on the host and rasterising every pixel there.  4 launches, no allocation, no host
+ * synchronisation, no launch count or grid that depends on the data, integer atomics only: equal inputs (the state and
+ * the map among them) give equal bytes.
+ * disp [H,W], K = (fx, fy, cx, cy), calib, labels [h,w] and ground_record (DEVICE, read on the device) exactly as
+ * codd_objects takes them.  ego_record: the DEVICE pointer to the 16 fp32 of this frame's codd_ego_motion (t = [0:3] in the
+ * unit of calib, q_xyzw = [3:7], ok = [7]; G: X_cur = R(q) X_prev + t), or NULL for a frame without a field.  fresh != 0:
+ * the first frame of a sequence.
+ * The map frame is the floor frame of the first integrated frame: the origin under the camera, z along that frame's f, x
+ * along r = f x n.  The axes stay: the grid never rotates and is never resampled.  The window has gw x gh cells of `cell`
+ * units and moves by whole cells.
+ * Caller-owned, persistent, DEVICE (zero them once; afterwards only this entry writes them):
+ *   logodds int16 [gh,gw], age uint8 [gh,gw]: toroidal storage, world cell (ix, iz) lives at row iz mod gh, column ix mod gw
+ *     (the mathematical modulo, also for negatives).  age 255: never observed inside the current window; otherwise the
+ *     number of frames since the last observation, saturating at 254.
+ *   state, 32 doubles: [0] EXISTS (a pose, a map and a stored floor frame exist); [1:3] (px, pz), the camera's foot point
+ *     in the map; [3:5] (hx, hz), the unit heading: the camera's floor-forward axis in the map, its floor-right axis being
+ *     (hz, -hx); [5:7] (ix0, iz0), the window origin: out[0,0]'s world cell; [7] frames since the last reset; [8] restarts;
+ *     [9:12] n, [12] Hc, [13:16] f: the last floor frame in the last camera's coordinates; and what launch 1 leaves for the
+ *     later ones: [16:18] the window origin before this call; [18] CLEARED (this call reset the map); [19] INTEGRATED;
+ *     [20] LINKED; [21:23] (dx, dz); [23:32] zero.
+ * Launch 1, the pose: fp64 throughout, the operations in the order written, none fused.
+ *   cur = ground_record[3] != 0: the current floor frame (n_c, Hc_c, f_c) = record [8:11], [11], [22:25].
+ *   The step is tried iff EXISTS && ego_record != NULL && !fresh && ego_record[7] != 0:  q / sqrt(((qx qx + qy qy) + qz qz) +
+ *   qw qw) (the step fails unless that root is finite and > 0);  R00 = 1 - 2 (qy qy + qz qz), R01 = 2 (qx qy - qz qw), R02 = 2
+ *   (qx qz + qy qw), R10 = 2 (qx qy + qz qw), R11 = 1 - 2 (qx qx + qz qz), R12 = 2 (qy qz - qx qw), R20 = 2 (qx qz - qy qw), R21 =
+ *   2 (qy qz + qx qw), R22 = 1 - 2 (qx qx + qy qy);  every 3-term sum below is (a + b) + c.  Without a current floor the
+ *   stored one is carried through G: n_c = R n_p;  Hc_c = Hc_p - n_c.t;  g = (-n2 n0, -n2 n1, 1 - n2 n2);  f_c = g / |g| (the
+ *   step fails unless |g| >= 1e-3).  r_p = f_p x n_p (codd_objects' expressions);  c = -(R^T t);  dx = r_p.c;  dz = f_p.c;
+ *   v = R^T f_c;  a = r_p.v;  b = f_p.v;  m = sqrt(a a + b b) (the step fails unless m >= 1e-6);
+ *   p' = ((px + dx hz) + dz hx, (pz - dx hx) + dz hz);  u = ((a hz + b hx) / m, (b hz - a hx) / m);  h' = u / sqrt(ux ux + uz uz);
+ *   the step fails unless |p'x / cell| and |p'z / cell| are < 2^30 and |u| is finite and > 0.  Only each frame's own floor
+ *   normal levels the step: roll and pitch errors do not accumulate.  No trigonometric function is used.
+ *   A step that succeeded: LINKED = 1, the pose advances, the stored floor frame becomes (n_c, Hc_c, f_c), frames += 1,
+ *   INTEGRATED = cur.  Otherwise the frame is LOST (LINKED = 0, dx = dz = 0):
+ *     lost == CODD_MAP_HOLD && EXISTS && !fresh: pose and map stay as if the camera stood still; the stored floor frame
+ *       becomes the current one when there is one; frames += 1; INTEGRATED = cur.
+ *     otherwise a reset: CLEARED = 1, p = (0, 0), h = (0, 1), frames = 0, restarts += 1 if EXISTS || fresh; with a current
+ *       floor EXISTS = 1, the stored floor frame is the current one and INTEGRATED = 1; without one EXISTS = 0, the stored
+ *       frame is zero and INTEGRATED = 0.
+ *   ix0 = floor(px / cell) - gw / 2;  iz0 = floor(pz / cell) - gh / 2  (cell as a double, gw / 2 the integer quotient).
+ * Launch 2, cells: every cell of the new window that was not in the old one -- all of them when CLEARED -- gets logodds 0,
+ *   age 255.  The per-frame tables O, F (int32 [gh,gw] in the scratch, in the order of the outputs) and the counters are
+ *   zeroed.
+ * Launch 3, pixels, iff INTEGRATED.  Every operation is one fp32 operation rounded on its own (no fused multiply-add;
+ *   sqrtf and division correctly rounded) unless it says fp64.  A pixel of the h x w crop is ELIGIBLE iff labels[y,x] ==
+ *   CODD_GROUND_FLOOR (a FLOOR pixel) or labels[y,x] < 32 && (select >> labels[y,x]) & 1 (an OBSTACLE pixel; select is
+ *   codd_objects' bit set and must not contain the floor), d = disp[y,x] is finite and > 0, and rho = sqrtf((gx * gx) + (gz *
+ *   gz)) >= range_min && rho < range_max, with gx, gz the expressions of codd_objects' "per pixel" paragraph, verbatim (the
+ *   bits codd_range_scan uses).  oxf = (float)(px - ix0 cell), ozf = (float)(pz - iz0 cell) (fp64, then rounded once); hxf =
+ *   (float)hx, hzf = (float)hz;  wx = (gx * hzf + gz * hxf) + oxf;  wz = (gz * hzf - gx * hxf) + ozf;  jx = floorf(wx / cell);
+ *   jz = floorf(wz / cell);  a pixel outside [0, gw) x [0, gh) (compared as floats; NaN is outside) is dropped; an obstacle
+ *   pixel adds 1 to O[jz,jx], a floor pixel to F[jz,jx].
+ * Launch 4, per window cell (j, i), world cell (ix0 + i, iz0 + j), integers only, in this order:
+ *   O >= min_pixels: L = min(L + l_occ, l_max), age = 0;  else F >= min_pixels: L = max(L - l_free, l_min), age = 0;
+ *   otherwise age = min(age + 1, 254) unless it is 255, and with decay > 0, L = max(L - decay, 0) for L > 0, min(L + decay, 0)
+ *   otherwise.  (A frame that is not INTEGRATED has empty tables: every cell ages and decays.)
+ *   map_out int16 [gh,gw], age_out uint8 [gh,gw]: the unrolled map, out[j,i] = world cell (ix0 + i, iz0 + j), every element
+ *   rewritten on every call.
+ *   record, 16 doubles, never NaN: [0] INTEGRATED, [1] LINKED, [2] restarts, [3] frames, [4:8] px, pz, hx, hz, [8:10] ix0, iz0,
+ *   [10] pixels integrated (the sum of O and F), [11] cells with L >= occ_level, [12] cells with L <= free_level, [13] cells
+ *   with age 255, [14:16] dx, dz.  The counts are integer atomic sums.
+ * scratch: codd_local_map_scratch(gh, gw) bytes (-1 for gh or gw outside [1, 4096] or gh gw > 2^22), 8 per cell plus the
+ * counters and the alignment, contents irrelevant, any alignment.  state and record need the alignment of a double,
+ * logodds and map_out that of an int16.
+ * CODD_EINVAL, before any launch: disp, labels, ground_record, state, logodds, age, scratch, map_out, age_out or record NULL;
+ * a non-positive size, h > H, w > W or h w >= 2^31; gh, gw outside the limits above; fx, fy, calib, cell or range_max not
+ * finite and > 0; cx or cy not finite; range_min negative, NaN or >= range_max; select with the bit of CODD_GROUND_FLOOR
+ * (0 is allowed: only the floor is mapped); min_pixels < 1; l_occ, l_free or decay outside [0, 32767]; l_min outside
+ * [-32768, 0]; l_max outside [0, 32767]; lost neither CODD_MAP_RESET nor CODD_MAP_HOLD; scratch_bytes below the size
+ * function's answer. */
+#define CODD_MAP_RESET 0
+#define CODD_MAP_HOLD 1
+long long codd_local_map_scratch(int gh, int gw);
+int codd_local_map(const float* disp, int H, int W, int h, int w, float fx, float fy, float cx, float cy, float calib,
+                   const unsigned char* labels, const double* ground_record, const float* ego_record, int fresh, int gh,
+                   int gw, float cell, float range_min, float range_max, unsigned select, int min_pixels, int l_occ,
+                   int l_free, int l_min, int l_max, int decay, int occ_level, int free_level, int lost, double* state,
+                   short* logodds, unsigned char* age, void* scratch, long long scratch_bytes, short* map_out,
+                   unsigned char* age_out, double* record, void* stream);
+
 /* Ablation plug-ins.  codd_fusion_select: mode 0 = KalmanFusion (model/fusion/others.py:124-153; constant
  * gain K = Q/(Q+R), the reference never updates P), mode 1 = GTFusion (:54-86; gt [B,1,hg,wg], zero-padded).
  * cur, warp, out: [B,1,H,W]. */
