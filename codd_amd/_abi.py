@@ -162,6 +162,8 @@ SIGNATURES = {
     "codd_local_map_scratch": (_ll, [_i, _i]),
     "codd_local_map": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _i, _i, _i, _f, _f, _f, C.c_uint, _i, _i, _i, _i, _i,
                             _i, _i, _i, _i, _p, _p, _p, _p, _ll, _p, _p, _p, _p]),
+    "codd_cost_map_scratch": (_ll, [_i, _i, _i]),
+    "codd_cost_map": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _p, _ll, _p, _p, _p, _p, _p, _p]),
     "codd_align_depth": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, C.POINTER(AlignView), _i, _i, _i, _p, _p, _p]),
 }
 

@@ -101,6 +101,13 @@ def parse_args(argv=None):
                         "float64 [1, frames, 4] (x, z and the unit heading in the map), origin int64 [1, frames, 2] (the world "
                         "cell of [0,0]), integrated, linked, restarts, occupied, free and unknown int32 [1, frames], cell, "
                         "occ_level and free_level")
+    p.add_argument("--costmap", action="store_true",
+                   help="--localmap: clearance, inflated cost, reachable cells and frontiers of every frame's local map; also "
+                        "write <name>.costmap.pred.npz: cost and reach uint8 and dist2 int32 [1, frames, gh, gw] (cost as ROS "
+                        "costmap_2d: 254 lethal, 253 inscribed, 255 no information; dist2 2^31 - 1: far; reach 1: reachable, 2: "
+                        "a frontier), occupied, inscribed, unknown, reachable, frontiers, start_ok, start_dist2 and frontier_dist2 "
+                        "int32 [1, frames], frontier_cell int32 [1, frames, 2] (j, i; -1: none), start (i, j), cell, robot_radius "
+                        "and inflation_radius")
     p.add_argument("--align-footprint", type=int, default=None, choices=[1, 2, 3, 4],
                    help="--align: target pixels per source pixel and axis (default: the smallest that leaves no hole lines)")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
@@ -162,6 +169,8 @@ def parse_args(argv=None):
         p.error("--scan needs --ground")
     if args.localmap and not (args.ground and args.ego):
         p.error("--localmap needs --ground and --ego")
+    if args.costmap and not args.localmap:
+        p.error("--costmap needs --localmap")
     if args.ground_grid is not None:
         m = re.fullmatch(r"(\d+)x(\d+)", args.ground_grid)
         if not m or not int(m.group(1)) or not int(m.group(2)):
@@ -338,7 +347,8 @@ def run_live(args, model, videos):
     --show; the id maps with --show only) and, with --tracks, <name>.tracks.pred.npz (per-frame n, continued, started, ended
     and the track tables padded to max_objects, written with or without --show) and, with --scan, <name>.scan.pred.npz
     (per-frame ranges, free ranges, objects and counts, written with or without --show) and, with --localmap,
-    <name>.localmap.pred.npz (per-frame map, age plane, pose and counts, written with or without --show).  With --pixel-format the
+    <name>.localmap.pred.npz (per-frame map, age plane, pose and counts, written with or without --show) and, with --costmap,
+    <name>.costmap.pred.npz (per-frame cost, dist2, reach, counts and nearest frontier, likewise).  With --pixel-format the
     frame files are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU.  With
     --calibration the frames (files or --frame-size) have the calibration's source size and every result has --net-size."""
     from PIL import Image
@@ -370,6 +380,8 @@ def run_live(args, model, videos):
         extra["scan"] = True
     if getattr(args, "localmap", False):
         extra["localmap"] = True
+    if getattr(args, "costmap", False):
+        extra["costmap"] = True
     raw = getattr(args, "pixel_format", None)
     if raw:
         extra.update(pixel_format=raw, pitch=args.pitch, yuv=args.yuv or "bt601")
@@ -409,11 +421,14 @@ def run_live(args, model, videos):
             if align_to:
                 aligned = _NpzStream(osp.join(args.show_dir, name + ".aligned.pred.npz"), "depth",
                                      (1, nf) + s.align_target.camera.size, np.float32)
-        n, epis, grounds, objs, trks, scans, maps = 0, [], [], [], [], [], []
+        n, epis, grounds, objs, trks, scans, maps, costs = 0, [], [], [], [], [], [], []
         try:
             frames = iter_raw_frames(lefts, rights, raw, src, args.pitch) if raw else iter_frames(lefts, rights)
             for res in live_results(s, frames):
                 n += 1
+                if "costmap" in extra:
+                    res, cm = res[:-1], res[-1]  # (a LocalMap precedes it: still a tuple)
+                    costs.append(cm)
                 if "localmap" in extra:
                     res, lm = res[:-1], res[-1]  # (an Ego and a Ground precede it: still a tuple)
                     maps.append(lm)
@@ -558,6 +573,22 @@ def run_live(args, model, videos):
             print(f"{name}: localmap: {gh} x {gw} cells; {sum(lm.integrated for lm in maps)} integrated, "
                   f"{sum(lm.linked for lm in maps)} linked in {len(maps)} frames, {maps[-1].restarts if maps else 0} restarts"
                   + (f", {maps[-1].occupied} occupied and {maps[-1].free} free cells at the end" if maps else ""))
+        if "costmap" in extra:
+            os.makedirs(args.show_dir, exist_ok=True)
+            np.savez(osp.join(args.show_dir, name + ".costmap.pred.npz"),
+                     cost=np.array([[cm.cost for cm in costs]], np.uint8), dist2=np.array([[cm.dist2 for cm in costs]], np.int32),
+                     reach=np.array([[cm.reach for cm in costs]], np.uint8),
+                     **{k: np.array([[int(getattr(cm, k)) for cm in costs]], np.int32)
+                        for k in ("occupied", "inscribed", "unknown", "reachable", "frontiers", "start_ok", "start_dist2",
+                                  "frontier_dist2")},
+                     frontier_cell=np.array([[cm.frontier_cell or (-1, -1) for cm in costs]], np.int32).reshape(1, len(costs), 2),
+                     start=np.array(costs[0].start if costs else (-1, -1), np.int32), cell=np.array(s.localmap["cell"], np.float64),
+                     robot_radius=np.array(s.costmap["robot_radius"], np.float64),
+                     inflation_radius=np.array(s.costmap["inflation_radius"], np.float64))
+            near = [cm.frontier_dist2 for cm in costs if cm.frontier_cell is not None]
+            print(f"{name}: costmap: start traversable in {sum(cm.start_ok for cm in costs)} of {len(costs)} frames"
+                  + (f", {costs[-1].reachable} reachable cells and {costs[-1].frontiers} frontiers at the end" if costs else "")
+                  + (f", nearest frontier {np.sqrt(min(near)) * s.localmap['cell']:.3f}" if near else ""))
         print(f"{name}: {n} frames")
     for s in sessions.values():
         s.close()

@@ -74,6 +74,11 @@ With ``localmap=`` (which needs ``ground=`` and ``egomotion=``) the session keep
 runs after ``codd_ground_plane`` and ``codd_ego_motion`` on their device records and labels, advances the camera's planar
 pose by the ego fit levelled with each frame's own floor normal, and adds the frame's floor and obstacle pixels to a rolling
 occupancy grid of integer log-odds that follows the camera.  The map, its age plane and the pose state stay on the device.
+
+With ``costmap=`` (which needs ``localmap=``) the session says where the robot can go: ``codd_cost_map`` runs right after
+``codd_local_map`` on the unrolled map it left on the device and returns, per cell, the squared distance to the nearest
+occupied cell, an inflated cost in the convention of ROS costmap_2d, whether the cell can be reached from the camera's cell,
+and whether the known space ends there (a frontier).  Integers only: equal maps give equal bytes.
 """
 from collections import deque, namedtuple
 
@@ -104,6 +109,11 @@ SCAN_DEFAULTS = dict(beams=256, angles_deg=None, range_min=0.0, range_max=12.8, 
 LOCALMAP_DEFAULTS = dict(grid=(128, 128), cell=0.1, range_min=0.0, range_max=12.8, select=("obstacle",), min_pixels=4, l_occ=4,
                          l_free=2, l_min=-32, l_max=64, decay=0, occ_level=8, free_level=-4, lost="reset")
 LOCALMAP_LOST = dict(reset=ops.MAP_RESET, hold=ops.MAP_HOLD)
+# Chosen by reasoning, not measured on real footage: a robot of 0.3 radius; costs that decay out to 1.0, where scaling 3.0
+# leaves 252 exp(-2.1) = 30, a visible slope across the seven cells of 0.1 in between; start_radius covers the blind zone of
+# a camera about 1 m above the floor, whose lower image edge meets the floor more than a metre ahead, so the cells under
+# and right around the robot are never observed.
+COSTMAP_DEFAULTS = dict(robot_radius=0.3, inflation_radius=1.0, scaling=3.0, start_radius=1.5, through_unknown=False, nearest=False)
 OBJECT_LABELS = dict(floor=ops.GROUND_FLOOR, obstacle=ops.GROUND_OBSTACLE, overhead=ops.GROUND_OVERHEAD,
                      below=ops.GROUND_BELOW)  # the names ``select`` takes
 
@@ -280,6 +290,51 @@ def localmap_from_buffers(record, map_out, age_out, cell, occ_level, free_level)
     return LocalMap(np.array(map_out, np.int16), np.array(age_out, np.uint8), (float(r[4]), float(r[5]), (float(r[6]), float(r[7]))),
                     (int(r[8]), int(r[9])), float(cell), bool(r[0] != 0), bool(r[1] != 0), int(r[2]), int(r[3]), int(r[11]),
                     int(r[12]), int(r[13]), int(r[10]), (float(r[14]), float(r[15])), int(occ_level), int(free_level))
+
+
+# One frame's cost map of the LocalMap of the same frame, caller-owned; [j,i] is the LocalMap's cell [j,i].  cost uint8
+# [gh,gw] in the convention of ROS costmap_2d (ops.COST_LETHAL 254: occupied, ops.COST_INSCRIBED 253: within robot_radius of
+# an occupied cell, 1 .. 252 decaying to inflation_radius, 0 free, ops.COST_NO_INFO 255: unknown and not inscribed); dist2
+# int32 [gh,gw]: the squared distance in cells to the nearest occupied cell of the window, ops.COST_FAR beyond R =
+# ceil(inflation_radius / cell) cells; nearest int32 [gh,gw] (the raster index j gw + i of that cell, -1 for none) or None
+# without ``nearest``; reach uint8 [gh,gw]: REACH_NO 0, REACH_YES 1, REACH_FRONTIER 2 (reachable, next to unknown cells that
+# are not); origin and cell as the LocalMap's; start = (i, j): the camera's cell; occupied, inscribed (cost 253 or 254),
+# unknown (cost 255), reachable (frontiers included) and frontiers: cell counts; start_ok: the start cell is traversable;
+# start_dist2: dist2 there (-1: far); frontier_cell = (j, i) of the frontier nearest to the start, or None; frontier_dist2:
+# its squared distance in cells (-1).
+_CostMap = namedtuple("CostMap", "cost dist2 nearest reach origin cell start occupied inscribed unknown reachable frontiers "
+                                 "start_ok start_dist2 frontier_cell frontier_dist2")
+REACH_NO, REACH_YES, REACH_FRONTIER = 0, 1, 2  # the values of CostMap.reach
+
+
+class CostMap(_CostMap):
+    __slots__ = ()
+
+    def clearance(self):
+        """fp32 [gh,gw]: the distance to the nearest occupied cell, sqrt(dist2) * cell, +inf where dist2 is far."""
+        far = self.dist2 == ops.COST_FAR
+        out = (np.sqrt(np.where(far, 0, self.dist2).astype(np.float64)) * self.cell).astype(np.float32)
+        out[far] = np.inf
+        return out
+
+    world_xz = LocalMap.world_xz  # (the same cells: it reads ``origin`` and ``cell`` alone)
+
+    def frontier_xz(self):
+        """The centre (x, z) of ``frontier_cell`` in the map frame, or None without a frontier."""
+        return None if self.frontier_cell is None else self.world_xz(*self.frontier_cell)
+
+
+def costmap_from_buffers(record, dist2, cost, reach, nearest, origin, cell, start):
+    """record float64 [16], dist2 int32, cost and reach uint8 [gh,gw] and nearest int32 [gh,gw] or None of codd_cost_map
+    (include/codd_hip.h), the LocalMap's ``origin`` and ``cell`` and start = (i, j) -> ``CostMap`` (copies: the buffers may be
+    reused)."""
+    r = np.asarray(record, np.float64)
+    gw = int(np.asarray(cost).shape[1])
+    front = int(r[8])
+    return CostMap(np.array(cost, np.uint8), np.array(dist2, np.int32), None if nearest is None else np.array(nearest, np.int32),
+                   np.array(reach, np.uint8), (int(origin[0]), int(origin[1])), float(cell), (int(start[0]), int(start[1])),
+                   int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), bool(r[5] != 0), int(r[6]),
+                   None if front < 0 else (front // gw, front % gw), int(r[9]))
 
 
 def _unit_up(up, pitch_deg=0.0):
@@ -683,6 +738,49 @@ def _check_localmap(localmap, ground=True, egomotion=True):
     return p
 
 
+def _check_costmap(costmap, localmap=True):
+    """False / None -> None; True -> the defaults; a dict overrides them.  ``localmap``: the checked ``localmap`` dict.
+    ValueError otherwise, and for ``costmap`` without ``localmap`` (no device call)."""
+    if costmap is None or costmap is False:
+        return None
+    if not (costmap is True or isinstance(costmap, dict)):
+        raise ValueError(f"costmap: False, True or a dict of {tuple(COSTMAP_DEFAULTS)} expected, got {costmap!r}")
+    if localmap is None or localmap is False:
+        raise ValueError("costmap: needs localmap= (the cost map is computed from the local map's cells)")
+    cell = float(localmap["cell"]) if isinstance(localmap, dict) else LOCALMAP_DEFAULTS["cell"]
+    unknown = set(costmap) - set(COSTMAP_DEFAULTS) if isinstance(costmap, dict) else ()
+    if unknown:
+        raise ValueError(f"costmap: unknown keys {sorted(unknown)}; known: {tuple(COSTMAP_DEFAULTS)}")
+    p = dict(COSTMAP_DEFAULTS, **(costmap if isinstance(costmap, dict) else {}))
+    for k in ("robot_radius", "inflation_radius", "scaling", "start_radius"):
+        try:
+            if isinstance(p[k], bool):
+                raise TypeError
+            p[k] = float(p[k])
+        except (TypeError, ValueError):
+            raise ValueError(f"costmap: a number expected for {k}, got {p[k]!r}") from None
+        if not np.isfinite(p[k]):
+            raise ValueError(f"costmap: a finite {k} expected, got {p[k]!r}")
+    if not p["inflation_radius"] > 0:
+        raise ValueError(f"costmap: positive inflation_radius expected, got {p['inflation_radius']!r}")
+    if not 0 <= p["robot_radius"] <= p["inflation_radius"]:
+        raise ValueError(f"costmap: 0 <= robot_radius <= inflation_radius expected, got {p['robot_radius']!r}, "
+                         f"{p['inflation_radius']!r}")
+    if not p["scaling"] >= 0:
+        raise ValueError(f"costmap: scaling >= 0 expected, got {p['scaling']!r}")
+    if not p["start_radius"] >= 0:
+        raise ValueError(f"costmap: start_radius >= 0 expected, got {p['start_radius']!r}")
+    for k in ("through_unknown", "nearest"):
+        if not isinstance(p[k], (bool, np.bool_)):
+            raise ValueError(f"costmap: a boolean expected for {k}, got {p[k]!r}")
+        p[k] = bool(p[k])
+    if np.ceil(p["inflation_radius"] / cell) > ops.COST_MAX_R:
+        raise ValueError(f"costmap: ceil(inflation_radius / cell) <= {ops.COST_MAX_R} expected, got {p['inflation_radius']!r} / {cell!r}")
+    if not (p["start_radius"] / cell) ** 2 < 2 ** 31:
+        raise ValueError(f"costmap: (start_radius / cell)^2 < 2^31 expected, got {p['start_radius']!r} / {cell!r}")
+    return p
+
+
 def scan_span(p, K, w):
     """(angle_min, angle_max) in radians of the checked ``scan`` dict: ``angles_deg``, or the camera's own horizontal field
     atan((0 - cx) / fx) .. atan((w - 1 - cx) / fx)."""
@@ -827,8 +925,8 @@ class LiveSession:
 
     ``egomotion`` (False, True, or a dict overriding ``iters``, ``delta_px``, ``tau_px``, ``min_valid``): ``pop`` and
     ``step`` also return an ``Ego`` (or None for a frame without a field).  The tuple order is fixed:
-    ``result[, motion][, ego][, confidence][, aligned][, epipolar][, ground][, objects][, tracks][, scan][, localmap]``,
-    each part present iff requested.
+    ``result[, motion][, ego][, confidence][, aligned][, epipolar][, ground][, objects][, tracks][, scan][, localmap]
+    [, costmap]``, each part present iff requested.
 
     ``confidence`` (False, True, or a dict overriding ``occ_px`` (1.0 pixel) and ``tau`` (24.0 grey levels)): ``pop`` and
     ``step`` also return a ``Confidence(flags, residual)`` on the CURRENT frame's grid, for every frame (never None).  It
@@ -926,12 +1024,24 @@ class LiveSession:
     ego fit that failed): ``"reset"`` starts a new map there, ``"hold"`` keeps map and pose as if the camera stood still.
     The first frame of a sequence starts a new map.  The defaults are reasoned, not measured on real footage.  Moving
     things are not excluded; free evidence and ``decay`` erase them.  Defined in include/codd_hip.h (codd_local_map).
+
+    ``costmap`` (False, True, or a dict overriding ``COSTMAP_DEFAULTS``; needs ``localmap``, ValueError without it): ``pop``
+    and ``step`` also return a ``CostMap`` of the frame's ``LocalMap``, for every frame (never None), last in the tuple.
+    Per cell: ``dist2``, the squared distance in cells to the nearest occupied cell within ``inflation_radius``; ``cost`` in
+    the convention of ROS costmap_2d -- 254 on an occupied cell, 253 within ``robot_radius`` of one, 252 exp(-``scaling``
+    (distance - ``robot_radius``)) (at least 1) out to ``inflation_radius``, 0 beyond, 255 on a cell that is neither
+    occupied nor free and not inscribed --; ``reach``, whether a robot at the camera's cell gets there over 4-neighbour
+    steps through free cells of cost below 253 (and unknown ones with ``through_unknown``), and whether the cell is a
+    frontier.  The cells within ``start_radius`` of the camera count as traversable unless occupied: the camera never
+    sees the floor under itself.  ``nearest`` also returns the nearest occupied cell's index.  The defaults are
+    reasoned, not measured on real footage.  Defined in include/codd_hip.h (codd_cost_map).
     """
 
     def __init__(self, estimator, shape, intrinsics=None, calib=None, output="depth",
                  bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False,
                  pixel_format="rgb8", yuv="bt601", pitch=None, calibration=None, zoom=1.0, align_to=None, align=None,
-                 epipolar=False, ground=False, objects=False, tracks=False, scan=False, localmap=False):
+                 epipolar=False, ground=False, objects=False, tracks=False, scan=False, localmap=False,
+                 costmap=False):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
@@ -948,6 +1058,7 @@ class LiveSession:
         self.tracks = _check_tracks(tracks, self.objects, estimator)
         self.scan = _check_scan(scan, self.ground)
         self.localmap = _check_localmap(localmap, self.ground, self.ego)
+        self.costmap = _check_costmap(costmap, self.localmap)
         h, w = int(shape[0]), int(shape[1])
         if h <= 0 or w <= 0:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
@@ -998,6 +1109,14 @@ class LiveSession:
             lm = self.localmap
             self._map_par = dict({k: lm[k] for k in ops.MAP_PARAMS if k not in ("select", "lost")},
                                  select=select_mask(lm["select"]), lost=LOCALMAP_LOST[lm["lost"]])
+        if self.costmap is not None:
+            cm, (gh, gw) = self.costmap, self.localmap["grid"]
+            self._cost_R, self._cost_lut_host = ops.cost_lut(self.localmap["cell"], cm["robot_radius"], cm["inflation_radius"],
+                                                             cm["scaling"])
+            self._cost_start = (gw // 2, gh // 2)  # the camera's cell, by the definition of ix0 and iz0
+            self._cost_par = dict(occ_level=self.localmap["occ_level"], free_level=self.localmap["free_level"],
+                                  seed_r2=int(np.floor((cm["start_radius"] / self.localmap["cell"]) ** 2)),
+                                  through_unknown=cm["through_unknown"])
         self.src_shape = (h, w) if self.rect is None else self.rect.size  # the size of a frame as the camera hands it out
         # (rows, row_bytes, pitch, nbytes) of a source frame; ValueError if invalid
         self._layout = frame_layout(pixel_format, self.src_shape[0], self.src_shape[1], pitch)
@@ -1129,6 +1248,16 @@ class LiveSession:
                 self._map_state = [torch.zeros(32, dtype=torch.float64, device=dev), torch.zeros(gh, gw, dtype=torch.int16, device=dev),
                                    torch.full((gh, gw), 255, dtype=torch.uint8, device=dev)]  # state, logodds, age
                 self._map_scratch = torch.empty(ops.local_map_scratch(gh, gw), dtype=torch.uint8, device=dev)
+            if self.costmap is not None:
+                gh, gw = self.localmap["grid"]
+                self._d_cost = [torch.zeros(16, dtype=torch.float64, device=dev), torch.zeros(gh, gw, dtype=torch.int32, device=dev),
+                                torch.zeros(gh, gw, dtype=torch.uint8, device=dev), torch.zeros(gh, gw, dtype=torch.uint8, device=dev)]
+                if self.costmap["nearest"]:  # record, dist2, cost, reach[, nearest]
+                    self._d_cost.append(torch.zeros(gh, gw, dtype=torch.int32, device=dev))
+                self._h_cost = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_cost]
+                                for _ in range(DEPTH)]
+                self._cost_lut = torch.from_numpy(self._cost_lut_host).to(dev)
+                self._cost_scratch = torch.empty(ops.cost_map_scratch(gh, gw, self._cost_R), dtype=torch.uint8, device=dev)
             self._s_up, self._s_down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             ev = lambda: [torch.cuda.Event() for _ in range(DEPTH)]  # noqa: E731
             self._e_up, self._e_ingest, self._e_export, self._e_down = ev(), ev(), ev(), ev()
@@ -1225,6 +1354,10 @@ class LiveSession:
                               self._d_ego[0] if Ts is not None else None, *self._map_state, self._d_map[1], self._d_map[2],
                               self._d_map[0], fresh=self._map_fresh, scratch=self._map_scratch, **self._map_par)
                 self._map_fresh = False
+                if self.costmap is not None:  # (on the unrolled map and age plane the call above left on the device)
+                    ops.cost_map(self._d_map[1], self._d_map[2], self._cost_lut, self._cost_R, self._cost_start, self._d_cost[1],
+                                 self._d_cost[4] if self.costmap["nearest"] else None, self._d_cost[2], self._d_cost[3],
+                                 self._d_cost[0], scratch=self._cost_scratch, **self._cost_par)
             if self.tracks is not None:  # (after the ego fit it reads, before export_motion rolls the depth map)
                 with_ego = self.ego is not None and Ts is not None
                 ops.track_objects(Ts, self._depth_prev, self._K, self.shape, self._object_ids(), self._d_objects[0],
@@ -1273,6 +1406,9 @@ class LiveSession:
                 if self.localmap is not None:
                     for host, dev_buf in zip(self._h_map[k], self._d_map):
                         host.copy_(dev_buf, non_blocking=True)
+                if self.costmap is not None:
+                    for host, dev_buf in zip(self._h_cost[k], self._d_cost):
+                        host.copy_(dev_buf, non_blocking=True)
                 self._e_down[k].record(self._s_down)
         self._inflight.append(k)
         self._pushed += 1
@@ -1309,6 +1445,10 @@ class LiveSession:
         if self.localmap is not None:
             lm = self.localmap
             out.append(localmap_from_buffers(*(t.numpy() for t in self._h_map[k]), lm["cell"], lm["occ_level"], lm["free_level"]))
+        if self.costmap is not None:
+            hc = [t.numpy() for t in self._h_cost[k]]
+            out.append(costmap_from_buffers(hc[0], hc[1], hc[2], hc[3], hc[4] if len(hc) > 4 else None, out[-1].origin,
+                                            self.localmap["cell"], self._cost_start))
         return out[0] if len(out) == 1 else tuple(out)
 
     def _object_ids(self):
@@ -1337,7 +1477,7 @@ class LiveSession:
         ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None; with ``egomotion``, an ``Ego`` or None
         follows; with ``confidence``, a ``Confidence``; with ``align_to``, an ``Aligned``; with ``epipolar``, an
         ``Epipolar``; with ``ground``, a ``Ground``; with ``objects``, an ``Objects``; with ``tracks``, a ``Tracks``; with
-        ``scan``, a ``Scan``; with ``localmap``, a ``LocalMap`` comes last."""
+        ``scan``, a ``Scan``; with ``localmap``, a ``LocalMap``; with ``costmap``, a ``CostMap`` comes last."""
         if self._ready:
             return self._ready.popleft()
         if not self._inflight:
@@ -1373,7 +1513,8 @@ class LiveSession:
                          "_d_epi", "_h_epi", "_epi_scratch", "_d_ground", "_h_ground", "_ground_scratch",
                          "_d_objects", "_h_objects", "_objects_scratch", "_track_ids", "_d_tracks", "_h_tracks",
                          "_track_state", "_track_scratch", "_d_scan", "_h_scan", "_scan_edges", "_scan_scratch",
-                         "_d_map", "_h_map", "_map_state", "_map_scratch"):
+                         "_d_map", "_h_map", "_map_state", "_map_scratch", "_d_cost", "_h_cost", "_cost_lut",
+                         "_cost_scratch"):
                 setattr(self, name, None)
             self._open_done = False
         self._inflight.clear()

@@ -2406,6 +2406,71 @@ def local_map(disp, K, calib, crop, labels, ground_record, ego_record, state, lo
     return record
 
 
+# CODD_COST_* of include/codd_hip.h: the cost values of ROS costmap_2d, the dist2 of a cell farther than R from every
+# obstacle, and the largest R
+COST_LETHAL, COST_INSCRIBED, COST_NO_INFO, COST_FAR, COST_MAX_R = 254, 253, 255, 0x7fffffff, 128
+
+
+def cost_lut(cell, robot_radius, inflation_radius, scaling):
+    """(R, lut): the table ``cost_map`` takes, uint8 [R R + 2], the cost by squared distance in cells.  R = max(1,
+    ceil(inflation_radius / cell)) (ValueError above ``COST_MAX_R``).  For n in 0 .. R R, with dist = sqrt(n) cell: 254 for
+    n == 0, 253 for dist <= robot_radius, max(1, int(252 exp(-scaling (dist - robot_radius)))) for dist <=
+    inflation_radius (ROS costmap_2d's inflation layer), 0 otherwise; lut[R R + 1] = 0 (farther than R).  numpy float64 on
+    the host, no device call."""
+    cell, robot_radius, inflation_radius, scaling = float(cell), float(robot_radius), float(inflation_radius), float(scaling)
+    if not (np.isfinite([cell, robot_radius, inflation_radius, scaling]).all() and cell > 0 and inflation_radius > 0
+            and 0 <= robot_radius <= inflation_radius and scaling >= 0):
+        raise ValueError(f"cost_lut: finite cell > 0, 0 <= robot_radius <= inflation_radius, inflation_radius > 0 and scaling >= 0 "
+                         f"expected, got {cell!r}, {robot_radius!r}, {inflation_radius!r}, {scaling!r}")
+    R = max(1, int(np.ceil(inflation_radius / cell)))
+    if R > COST_MAX_R:
+        raise ValueError(f"cost_lut: ceil(inflation_radius / cell) <= {COST_MAX_R} expected, got {R}")
+    dist = np.sqrt(np.arange(R * R + 1, dtype=np.float64)) * cell
+    decay = np.maximum(1, (252.0 * np.exp(-scaling * np.maximum(dist - robot_radius, 0.0))).astype(np.int64))  # (truncated)
+    lut = np.zeros(R * R + 2, np.uint8)
+    lut[:-1] = np.where(dist <= robot_radius, COST_INSCRIBED, np.where(dist <= inflation_radius, decay, 0))
+    lut[0] = COST_LETHAL
+    return R, lut
+
+
+def cost_map_scratch(gh, gw, R):
+    """Bytes of scratch ``cost_map`` needs (codd_cost_map_scratch)."""
+    n = int(_abi.load().codd_cost_map_scratch(int(gh), int(gw), int(R)))
+    if n <= 0:
+        raise ValueError(f"cost_map_scratch: gh, gw in [1, {MAP_MAX_SIDE}], gh gw <= 2^22 and R in [1, {COST_MAX_R}] expected, got "
+                         f"{gh}, {gw}, {R}")
+    return n
+
+
+def cost_map(map, age, lut, R, start, dist2, nearest, cost, reach, record, occ_level=MAP_PARAMS["occ_level"],
+             free_level=MAP_PARAMS["free_level"], seed_r2=0, through_unknown=False, scratch=None):
+    """Where can I go?  Clearance, inflated cost, reachable cells and frontiers of one occupancy map (include/codd_hip.h,
+    codd_cost_map).  ``map`` int16 [gh,gw] and ``age`` uint8 [gh,gw]: the ``map_out`` and ``age_out`` of ``local_map``;
+    ``lut`` uint8 [R R + 2] on the device (``cost_lut``); ``start`` = (start_i, start_j), the robot's cell (column, row).
+    Outputs, caller-owned device tensors: ``dist2`` int32 [gh,gw], ``nearest`` int32 [gh,gw] or None, ``cost`` and ``reach``
+    uint8 [gh,gw], ``record`` float64 [16].  ``scratch``: a uint8 tensor of ``cost_map_scratch`` bytes; allocated here when
+    None.  Five launches on the current stream, no host synchronisation."""
+    lib = _abi.load()
+    _require_gpu(map)
+    assert map.dim() == 2, "map: [gh,gw] expected"
+    gh, gw = int(map.shape[0]), int(map.shape[1])
+    R = int(R)
+    assert map.dtype == torch.int16 and map.is_cuda and map.is_contiguous()
+    assert lut.dtype == torch.uint8 and lut.is_cuda and lut.is_contiguous() and lut.numel() == R * R + 2
+    assert record.dtype == torch.float64 and record.is_cuda and record.is_contiguous() and record.numel() == 16
+    for t, dt in ((age, torch.uint8), (dist2, torch.int32), (cost, torch.uint8), (reach, torch.uint8)) + (
+            () if nearest is None else ((nearest, torch.int32),)):
+        assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (gh, gw)
+    if scratch is None:
+        scratch = torch.empty(cost_map_scratch(gh, gw, R), dtype=torch.uint8, device=map.device)
+    assert scratch.dtype == torch.uint8 and scratch.is_cuda and scratch.is_contiguous()
+    _abi.check(lib.codd_cost_map(map.data_ptr(), age.data_ptr(), gh, gw, int(occ_level), int(free_level), R, lut.data_ptr(),
+                                 int(start[0]), int(start[1]), int(seed_r2), 1 if through_unknown else 0, scratch.data_ptr(),
+                                 scratch.numel(), dist2.data_ptr(), None if nearest is None else nearest.data_ptr(),
+                                 cost.data_ptr(), reach.data_ptr(), record.data_ptr(), _stream()), "cost_map")
+    return record
+
+
 ALIGN_MAX_FOOTPRINT = 4  # CODD_ALIGN_MAX_FOOTPRINT of include/codd_hip.h
 
 

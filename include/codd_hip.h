@@ -1229,6 +1229,58 @@ int codd_local_map(const float* disp, int H, int W, int h, int w, float fx, floa
                    short* logodds, unsigned char* age, void* scratch, long long scratch_bytes, short* map_out,
                    unsigned char* age_out, double* record, void* stream);
 
+/* Live-session cost map (codd_amd/live.py, costmap=): what a local planner or a safety monitor makes of the occupancy map
+ * first.  Per cell of codd_local_map's unrolled window: the squared distance to the nearest occupied cell, an inflated
+ * cost (so that the robot can be treated as a point), whether the robot can reach the cell from where it stands, and
+ * whether the known space ends there (a frontier).  The reference has no such output; this replaces a download of the map
+ * every frame and a distance transform plus a flood fill on the host.  Everything is an integer and everything below
+ * defines the result, not the algorithm: equal inputs give equal bytes.  No allocation, no host synchronisation, no launch
+ * count or grid that depends on the data, integer atomics only; every output element is rewritten on every call.
+ * Inputs, all DEVICE, never written: map int16 [gh,gw] and age uint8 [gh,gw], the map_out / age_out of codd_local_map
+ * ([j,i]: row j, column i); lut uint8 [R R + 2], the cost by squared distance (codd_amd/ops.py cost_lut builds one).  gh, gw
+ * within codd_local_map's limits, R in [1, CODD_COST_MAX_R].
+ * The class of a cell: OCC iff map >= occ_level; otherwise FREE iff age != 255 && map <= free_level; otherwise UNKNOWN.
+ * dist2 int32 [gh,gw]: the minimum of (i - i')^2 + (j - j')^2 over the OCC cells (j', i') of the window (cells outside the
+ *   window are no sources) if that minimum is <= R R, else CODD_COST_FAR.
+ * nearest int32 [gh,gw], or NULL: the raster index j' gw + i' of an OCC cell that attains dist2, the smallest such index;
+ *   -1 where dist2 is CODD_COST_FAR.
+ * cost uint8 [gh,gw]: c = lut[dist2 <= R R ? dist2 : R R + 1]; the cost is c, except that an UNKNOWN cell with c <
+ *   CODD_COST_INSCRIBED gets CODD_COST_NO_INFO.  With cost_lut's table this is the convention of ROS costmap_2d: 254
+ *   lethal (an obstacle), 253 inscribed (the robot's centre there means a collision), 1 .. 252 decaying with the distance,
+ *   0 free, 255 no information.
+ * Traversable.  A cell is a SEED iff (i - start_i)^2 + (j - start_j)^2 <= seed_r2; a SEED cell is traversable iff it is not
+ *   OCC (the robot stands there, and a forward-looking camera never observes the floor under and right around itself:
+ *   without the seed disk the start cell is UNKNOWN in every real session and nothing is reachable).  Any other cell is
+ *   traversable iff c < CODD_COST_INSCRIBED (c as above, before the NO_INFO substitution) and it is FREE, or UNKNOWN with
+ *   through_unknown != 0.
+ * reach uint8 [gh,gw]: 0 not reachable; 1 traversable and joined to the start cell (start_j, start_i) by a 4-neighbour path
+ *   of traversable cells (the start cell itself when it is traversable); 2 reachable and a FRONTIER: one of its 4-neighbours
+ *   inside the window is UNKNOWN and not itself reachable.  If the start cell is OCC nothing is reachable.
+ * record, 16 doubles, never NaN; every count is an integer atomic sum: [0] OCC cells, [1] cells with cost 253 or 254, [2]
+ *   cells with cost 255, [3] reachable cells (frontiers included), [4] frontier cells, [5] 1 iff the start cell is
+ *   traversable, [6] dist2 at the start cell (-1 for CODD_COST_FAR), [7] nearest at the start cell (-1; also when nearest is
+ *   NULL), [8] the raster index of the frontier cell nearest to the start cell -- by (i - start_i)^2 + (j - start_j)^2, ties
+ *   to the smallest raster index, -1 if there is none: one 64-bit integer atomic minimum of (d2 << 32) | raster --, [9] that
+ *   cell's squared distance (-1), [10:16] zero.
+ * Five launches (column pass, row pass with the tile-local union-find, tile borders, flatten, reach; four for a window
+ * of one tile).
+ * scratch: codd_cost_map_scratch(gh, gw, R) bytes (-1 for gh, gw or R outside their limits), 7 per cell plus the counters
+ * and the alignment, contents irrelevant, any alignment.  dist2 and nearest need the alignment of an int32, map that of
+ * an int16, record that of a double.
+ * CODD_EINVAL, before any launch: map, age, lut, scratch, dist2, cost, reach or record NULL (nearest may be); gh, gw outside
+ * the limits; R outside [1, CODD_COST_MAX_R]; free_level >= occ_level; start_i outside [0, gw) or start_j outside [0, gh);
+ * seed_r2 < 0; scratch_bytes below the size function's answer. */
+#define CODD_COST_LETHAL 254
+#define CODD_COST_INSCRIBED 253
+#define CODD_COST_NO_INFO 255
+#define CODD_COST_FAR 0x7fffffff
+#define CODD_COST_MAX_R 128
+long long codd_cost_map_scratch(int gh, int gw, int R);
+int codd_cost_map(const short* map, const unsigned char* age, int gh, int gw, int occ_level, int free_level, int R,
+                  const unsigned char* lut, int start_i, int start_j, int seed_r2, int through_unknown, void* scratch,
+                  long long scratch_bytes, int* dist2, int* nearest, unsigned char* cost, unsigned char* reach,
+                  double* record, void* stream);
+
 /* Ablation plug-ins.  codd_fusion_select: mode 0 = KalmanFusion (model/fusion/others.py:124-153; constant
  * gain K = Q/(Q+R), the reference never updates P), mode 1 = GTFusion (:54-86; gt [B,1,hg,wg], zero-padded).
  * cur, warp, out: [B,1,H,W]. */
