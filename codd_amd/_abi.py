@@ -164,6 +164,9 @@ SIGNATURES = {
                             _i, _i, _i, _i, _p, _p, _p, _p, _ll, _p, _p, _p, _p]),
     "codd_cost_map_scratch": (_ll, [_i, _i, _i]),
     "codd_cost_map": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _p, _ll, _p, _p, _p, _p, _p, _p]),
+    "codd_plan_scratch": (_ll, [_i, _i]),
+    "codd_plan": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, _f, _i, _i, _i, _i, _i, _p, _ll, _p, _p,
+                       _p, _p, _p]),
     "codd_align_depth": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, C.POINTER(AlignView), _i, _i, _i, _p, _p, _p]),
 }
 

@@ -108,6 +108,14 @@ def parse_args(argv=None):
                         "a frontier), occupied, inscribed, unknown, reachable, frontiers, start_ok, start_dist2 and frontier_dist2 "
                         "int32 [1, frames], frontier_cell int32 [1, frames, 2] (j, i; -1: none), start (i, j), cell, robot_radius "
                         "and inflation_radius")
+    p.add_argument("--plan", action="store_true",
+                   help="--costmap: the navigation function and the path to the goal on every frame's cost map; also write "
+                        "<name>.plan.pred.npz: potential uint32 [1, frames, gh, gw] (0xffffffff: no path), path int32 [1, frames, "
+                        "max_path, 2] (j, i; -1 behind the last cell), found, cost, length_cells, truncated, clamped, snapped, "
+                        "reached and max_cost_on_path int32 [1, frames], goal_cell and end_cell int32 [1, frames, 2] (j, i; -1: none), "
+                        "length float64 [1, frames], start (i, j) and cell")
+    p.add_argument("--plan-goal", default="frontier", metavar="frontier|X,Z",
+                   help="--plan: the nearest frontier (default) or a point X,Z of the map frame")
     p.add_argument("--align-footprint", type=int, default=None, choices=[1, 2, 3, 4],
                    help="--align: target pixels per source pixel and axis (default: the smallest that leaves no hole lines)")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
@@ -171,6 +179,16 @@ def parse_args(argv=None):
         p.error("--localmap needs --ground and --ego")
     if args.costmap and not args.localmap:
         p.error("--costmap needs --localmap")
+    if args.plan and not args.costmap:
+        p.error("--plan needs --costmap")
+    if args.plan_goal != "frontier":
+        m = re.fullmatch(r"([^,]+),([^,]+)", args.plan_goal)
+        try:
+            args.plan_goal = (float(m.group(1)), float(m.group(2)))
+            if not all(np.isfinite(args.plan_goal)):
+                raise ValueError
+        except (AttributeError, ValueError):
+            p.error("--plan-goal: frontier or X,Z expected")
     if args.ground_grid is not None:
         m = re.fullmatch(r"(\d+)x(\d+)", args.ground_grid)
         if not m or not int(m.group(1)) or not int(m.group(2)):
@@ -348,7 +366,8 @@ def run_live(args, model, videos):
     and the track tables padded to max_objects, written with or without --show) and, with --scan, <name>.scan.pred.npz
     (per-frame ranges, free ranges, objects and counts, written with or without --show) and, with --localmap,
     <name>.localmap.pred.npz (per-frame map, age plane, pose and counts, written with or without --show) and, with --costmap,
-    <name>.costmap.pred.npz (per-frame cost, dist2, reach, counts and nearest frontier, likewise).  With --pixel-format the
+    <name>.costmap.pred.npz (per-frame cost, dist2, reach, counts and nearest frontier, likewise) and, with --plan,
+    <name>.plan.pred.npz (per-frame potential, path and counts, likewise).  With --pixel-format the
     frame files are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU.  With
     --calibration the frames (files or --frame-size) have the calibration's source size and every result has --net-size."""
     from PIL import Image
@@ -382,6 +401,8 @@ def run_live(args, model, videos):
         extra["localmap"] = True
     if getattr(args, "costmap", False):
         extra["costmap"] = True
+    if getattr(args, "plan", False):
+        extra["plan"] = dict(goal=getattr(args, "plan_goal", "frontier"))
     raw = getattr(args, "pixel_format", None)
     if raw:
         extra.update(pixel_format=raw, pitch=args.pitch, yuv=args.yuv or "bt601")
@@ -421,11 +442,14 @@ def run_live(args, model, videos):
             if align_to:
                 aligned = _NpzStream(osp.join(args.show_dir, name + ".aligned.pred.npz"), "depth",
                                      (1, nf) + s.align_target.camera.size, np.float32)
-        n, epis, grounds, objs, trks, scans, maps, costs = 0, [], [], [], [], [], [], []
+        n, epis, grounds, objs, trks, scans, maps, costs, plans = 0, [], [], [], [], [], [], [], []
         try:
             frames = iter_raw_frames(lefts, rights, raw, src, args.pitch) if raw else iter_frames(lefts, rights)
             for res in live_results(s, frames):
                 n += 1
+                if "plan" in extra:
+                    res, pl = res[:-1], res[-1]  # (a CostMap precedes it: still a tuple)
+                    plans.append(pl)
                 if "costmap" in extra:
                     res, cm = res[:-1], res[-1]  # (a LocalMap precedes it: still a tuple)
                     costs.append(cm)
@@ -589,6 +613,24 @@ def run_live(args, model, videos):
             print(f"{name}: costmap: start traversable in {sum(cm.start_ok for cm in costs)} of {len(costs)} frames"
                   + (f", {costs[-1].reachable} reachable cells and {costs[-1].frontiers} frontiers at the end" if costs else "")
                   + (f", nearest frontier {np.sqrt(min(near)) * s.localmap['cell']:.3f}" if near else ""))
+        if "plan" in extra:
+            os.makedirs(args.show_dir, exist_ok=True)
+            paths = np.full((1, len(plans), s.plan["max_path"], 2), -1, np.int32)
+            for k, pl in enumerate(plans):
+                paths[0, k, :len(pl.path)] = pl.path
+            np.savez(osp.join(args.show_dir, name + ".plan.pred.npz"),
+                     potential=np.array([[pl.potential for pl in plans]], np.uint32), path=paths,
+                     **{k: np.array([[int(getattr(pl, k)) for pl in plans]], np.int32)
+                        for k in ("found", "cost", "length_cells", "truncated", "clamped", "snapped", "reached", "max_cost_on_path")},
+                     goal_cell=np.array([[pl.goal_cell or (-1, -1) for pl in plans]], np.int32).reshape(1, len(plans), 2),
+                     end_cell=np.array([[pl.end_cell or (-1, -1) for pl in plans]], np.int32).reshape(1, len(plans), 2),
+                     length=np.array([[pl.length for pl in plans]], np.float64),
+                     start=np.array(plans[0].start if plans else (-1, -1), np.int32), cell=np.array(s.localmap["cell"], np.float64))
+            found = [pl for pl in plans if pl.found]
+            print(f"{name}: plan: a path to {'the nearest frontier' if s.plan['goal'] == 'frontier' else s.plan['goal']} in "
+                  f"{len(found)} of {len(plans)} frames"
+                  + (f", the last {found[-1].length:.3f} long over {found[-1].length_cells} cells at cost {found[-1].cost}, at most "
+                     f"cost {found[-1].max_cost_on_path} on it, {found[-1].reached} cells reached" if found else ""))
         print(f"{name}: {n} frames")
     for s in sessions.values():
         s.close()

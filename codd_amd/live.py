@@ -79,6 +79,11 @@ With ``costmap=`` (which needs ``localmap=``) the session says where the robot c
 ``codd_local_map`` on the unrolled map it left on the device and returns, per cell, the squared distance to the nearest
 occupied cell, an inflated cost in the convention of ROS costmap_2d, whether the cell can be reached from the camera's cell,
 and whether the known space ends there (a frontier).  Integers only: equal maps give equal bytes.
+
+With ``plan=`` (which needs ``costmap=``) the session says which way to go: ``codd_plan`` runs right after
+``codd_cost_map`` on the cost and reach it left on the device and returns the navigation function -- the least cost to reach
+the goal from every reachable cell -- and the path from the camera's cell to the goal.  The goal is the nearest frontier
+(exploring) or a point of the map frame, changed between frames with ``set_goal``.  Integers only, one launch.
 """
 from collections import deque, namedtuple
 
@@ -114,6 +119,12 @@ LOCALMAP_LOST = dict(reset=ops.MAP_RESET, hold=ops.MAP_HOLD)
 # a camera about 1 m above the floor, whose lower image edge meets the floor more than a metre ahead, so the cells under
 # and right around the robot are never observed.
 COSTMAP_DEFAULTS = dict(robot_radius=0.3, inflation_radius=1.0, scaling=3.0, start_radius=1.5, through_unknown=False, nearest=False)
+# Chosen by reasoning, not measured on real footage: neutral 50 and factor 0.8 (205 / 256) are the defaults of ROS navfn, so
+# a free cell costs 50 per step and an inscribed one 50 + 202 -- five free cells of detour buy one cell away from a wall;
+# an unknown cell (crossed only with the cost map's through_unknown) counts as cost 128, half way up; the goal is the
+# nearest frontier, which is what a robot without orders does; 1024 path cells cover the diagonal of the default window
+# more than five times.
+PLAN_DEFAULTS = dict(goal="frontier", goal_radius=0.0, neutral=50, factor=205, unknown_cost=128, max_path=1024, dir=False)
 OBJECT_LABELS = dict(floor=ops.GROUND_FLOOR, obstacle=ops.GROUND_OBSTACLE, overhead=ops.GROUND_OVERHEAD,
                      below=ops.GROUND_BELOW)  # the names ``select`` takes
 
@@ -335,6 +346,60 @@ def costmap_from_buffers(record, dist2, cost, reach, nearest, origin, cell, star
                    np.array(reach, np.uint8), (int(origin[0]), int(origin[1])), float(cell), (int(start[0]), int(start[1])),
                    int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), bool(r[5] != 0), int(r[6]),
                    None if front < 0 else (front // gw, front % gw), int(r[9]))
+
+
+# One frame's plan on the CostMap of the same frame, caller-owned; [j,i] is the LocalMap's cell [j,i].  potential uint32
+# [gh,gw]: the least cost to reach the goal from the cell (ops.PLAN_UNREACHED: no path), the sum over the cells entered of
+# the step's length (5 straight, 7 diagonal) times neutral + factor cost / 256; dir uint8 [gh,gw] or None without ``dir``: the
+# move to make there (0 .. 7: (di, dj) = PLAN_MOVES[k], 8: in the goal set, 255: no path); path int32 [n,2]: the cells (j, i)
+# from the start cell to the goal, the written entries only; found: the start cell has a path; cost: the potential there
+# (-1); length_cells: the cells of the full path; truncated: it is longer than max_path; goal_cell = (j, i) after clamping,
+# or None without a goal; clamped: the goal lay outside the window; snapped: no reachable cell lay within goal_radius of the
+# goal cell and the nearest reachable one took its place; end_cell = (j, i) of the path's last cell, or None; reached: the
+# cells with a path; max_cost_on_path: the largest cost byte other than 255 on the path (-1); length: the path's length in
+# the map's unit; origin and cell as the LocalMap's; start = (i, j): the camera's cell.
+_Plan = namedtuple("Plan", "potential dir path found cost length_cells truncated goal_cell clamped snapped end_cell reached "
+                           "max_cost_on_path length origin cell start")
+PLAN_MOVES = ((1, 0), (-1, 0), (0, 1), (0, -1), (1, 1), (-1, 1), (1, -1), (-1, -1))  # (di, dj) of Plan.dir's k
+
+
+class Plan(_Plan):
+    __slots__ = ()
+
+    world_xz = LocalMap.world_xz  # (the same cells: it reads ``origin`` and ``cell`` alone)
+
+    def path_xz(self):
+        """float64 [n,2]: the centres (x, z) of the path's cells in the map frame."""
+        if not len(self.path):
+            return np.zeros((0, 2), np.float64)
+        return np.stack(self.world_xz(self.path[:, 0], self.path[:, 1]), axis=1)
+
+    def lookahead(self, dist):
+        """The centre (x, z) of the first path cell at least ``dist`` from the start cell along the path (a straight step is
+        one cell long, a diagonal one 7 / 5), or of the last cell if none is; None without a path.  The point a pure-pursuit
+        controller steers at."""
+        if not len(self.path):
+            return None
+        step = np.abs(np.diff(self.path, axis=0)).sum(axis=1)  # 1: straight, 2: diagonal
+        along = np.concatenate(([0.0], np.cumsum(np.where(step == 1, 5, 7)) * (self.cell / 5.0)))
+        k = int(np.argmax(along >= dist)) if (along >= dist).any() else len(along) - 1
+        return self.world_xz(int(self.path[k, 0]), int(self.path[k, 1]))
+
+
+def plan_from_buffers(record, potential, dir, path, origin, cell, start):
+    """record float64 [16], potential [gh,gw] (its 32 bits, signed or not), dir uint8 [gh,gw] or None and path int32 [max_path]
+    of codd_plan (include/codd_hip.h), the LocalMap's ``origin`` and ``cell`` and start = (i, j) -> ``Plan`` (copies: the
+    buffers may be reused)."""
+    r = np.asarray(record, np.float64)
+    pot = np.array(np.asarray(potential).view(np.uint32))
+    gw = int(pot.shape[1])
+    n = int(r[3])
+    cells = np.array(np.asarray(path, np.int32)[:n])
+    at = lambda v: None if v < 0 else (int(v) // gw, int(v) % gw)  # noqa: E731
+    return Plan(pot, None if dir is None else np.array(dir, np.uint8), np.stack([cells // gw, cells % gw], axis=1).astype(np.int32),
+                bool(r[0] != 0), int(r[1]), int(r[2]), bool(r[2] > r[3]), at(r[4]), bool(r[5] != 0), bool(r[6] != 0), at(r[8]),
+                int(r[9]), int(r[11]), float(r[12]) * float(cell) / 5.0, (int(origin[0]), int(origin[1])), float(cell),
+                (int(start[0]), int(start[1])))
 
 
 def _unit_up(up, pitch_deg=0.0):
@@ -781,6 +846,58 @@ def _check_costmap(costmap, localmap=True):
     return p
 
 
+def _check_goal(goal):
+    """"frontier" or a finite (x, z) of the map frame -> "frontier" or (float, float).  ValueError otherwise."""
+    if isinstance(goal, str) and goal == "frontier":
+        return goal
+    try:
+        if isinstance(goal, str) or any(isinstance(v, bool) for v in goal):
+            raise TypeError
+        x, z = (float(v) for v in goal)
+    except (TypeError, ValueError):
+        raise ValueError(f'plan: goal "frontier" or (x, z) in the map frame expected, got {goal!r}') from None
+    if not (np.isfinite(x) and np.isfinite(z)):
+        raise ValueError(f"plan: a finite goal (x, z) expected, got {goal!r}")
+    return (x, z)
+
+
+def _check_plan(plan, costmap=True, localmap=True):
+    """False / None -> None; True -> the defaults; a dict overrides them.  ``costmap`` and ``localmap``: the checked dicts.
+    ValueError otherwise, for ``plan`` without ``costmap`` and for a grid above ``ops.PLAN_MAX_CELLS`` (no device call)."""
+    if plan is None or plan is False:
+        return None
+    if not (plan is True or isinstance(plan, dict)):
+        raise ValueError(f"plan: False, True or a dict of {tuple(PLAN_DEFAULTS)} expected, got {plan!r}")
+    if costmap is None or costmap is False:
+        raise ValueError("plan: needs costmap= (the plan is computed on the cost map's cost and reach)")
+    grid, cell = ((localmap["grid"], float(localmap["cell"])) if isinstance(localmap, dict)
+                  else (LOCALMAP_DEFAULTS["grid"], LOCALMAP_DEFAULTS["cell"]))
+    if int(grid[0]) * int(grid[1]) > ops.PLAN_MAX_CELLS:
+        raise ValueError(f"plan: a localmap grid of at most {ops.PLAN_MAX_CELLS} cells expected (the whole window is planned in "
+                         f"the LDS of one CU), got {tuple(grid)}")
+    unknown = set(plan) - set(PLAN_DEFAULTS) if isinstance(plan, dict) else ()
+    if unknown:
+        raise ValueError(f"plan: unknown keys {sorted(unknown)}; known: {tuple(PLAN_DEFAULTS)}")
+    p = dict(PLAN_DEFAULTS, **(plan if isinstance(plan, dict) else {}))
+    p["goal"] = _check_goal(p["goal"])
+    try:
+        if isinstance(p["goal_radius"], bool):
+            raise TypeError
+        p["goal_radius"] = float(p["goal_radius"])
+    except (TypeError, ValueError):
+        raise ValueError(f"plan: a number expected for goal_radius, got {p['goal_radius']!r}") from None
+    if not (np.isfinite(p["goal_radius"]) and p["goal_radius"] >= 0 and (p["goal_radius"] / cell) ** 2 < 2 ** 31):
+        raise ValueError(f"plan: finite goal_radius >= 0 with (goal_radius / cell)^2 < 2^31 expected, got {p['goal_radius']!r}")
+    for k, lo, hi in (("neutral", 1, 255), ("factor", 0, 1024), ("unknown_cost", 0, 254), ("max_path", 1, 2 ** 31 - 1)):
+        if isinstance(p[k], (bool, np.bool_)) or not isinstance(p[k], (int, np.integer)) or not lo <= p[k] <= hi:
+            raise ValueError(f"plan: an integer in [{lo}, {hi}] expected for {k}, got {p[k]!r}")
+        p[k] = int(p[k])
+    if not isinstance(p["dir"], (bool, np.bool_)):
+        raise ValueError(f"plan: a boolean expected for dir, got {p['dir']!r}")
+    p["dir"] = bool(p["dir"])
+    return p
+
+
 def scan_span(p, K, w):
     """(angle_min, angle_max) in radians of the checked ``scan`` dict: ``angles_deg``, or the camera's own horizontal field
     atan((0 - cx) / fx) .. atan((w - 1 - cx) / fx)."""
@@ -926,7 +1043,7 @@ class LiveSession:
     ``egomotion`` (False, True, or a dict overriding ``iters``, ``delta_px``, ``tau_px``, ``min_valid``): ``pop`` and
     ``step`` also return an ``Ego`` (or None for a frame without a field).  The tuple order is fixed:
     ``result[, motion][, ego][, confidence][, aligned][, epipolar][, ground][, objects][, tracks][, scan][, localmap]
-    [, costmap]``, each part present iff requested.
+    [, costmap][, plan]``, each part present iff requested.
 
     ``confidence`` (False, True, or a dict overriding ``occ_px`` (1.0 pixel) and ``tau`` (24.0 grey levels)): ``pop`` and
     ``step`` also return a ``Confidence(flags, residual)`` on the CURRENT frame's grid, for every frame (never None).  It
@@ -1035,13 +1152,24 @@ class LiveSession:
     frontier.  The cells within ``start_radius`` of the camera count as traversable unless occupied: the camera never
     sees the floor under itself.  ``nearest`` also returns the nearest occupied cell's index.  The defaults are
     reasoned, not measured on real footage.  Defined in include/codd_hip.h (codd_cost_map).
+
+    ``plan`` (False, True, or a dict overriding ``PLAN_DEFAULTS``; needs ``costmap``, ValueError without it and for a
+    ``localmap`` grid above ``ops.PLAN_MAX_CELLS`` cells): ``pop`` and ``step`` also return a ``Plan`` on the frame's
+    ``CostMap``, for every frame (never None), last in the tuple.  ``goal`` is ``"frontier"`` (the frontier nearest to the
+    camera, for exploring) or a point ``(x, z)`` of the map frame, which is clamped into the window when it lies outside;
+    ``set_goal`` changes it for the frames pushed afterwards.  The goal set is the reachable cells within ``goal_radius``
+    of the goal cell, or the reachable cell nearest to it when there are none.  ``potential`` is the least cost from every
+    reachable cell to the goal set over 8-neighbour moves that cut no corner, a step of length 5 (straight) or 7
+    (diagonal) into a cell costing ``neutral`` + ``factor`` cost / 256 (``unknown_cost`` for cost 255); ``path`` the cells
+    from the camera's cell to the goal, at most ``max_path``; ``dir`` also returns the move to make at every cell.  The
+    defaults are navfn's and are reasoned, not measured on real footage.  Defined in include/codd_hip.h (codd_plan).
     """
 
     def __init__(self, estimator, shape, intrinsics=None, calib=None, output="depth",
                  bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False,
                  pixel_format="rgb8", yuv="bt601", pitch=None, calibration=None, zoom=1.0, align_to=None, align=None,
                  epipolar=False, ground=False, objects=False, tracks=False, scan=False, localmap=False,
-                 costmap=False):
+                 costmap=False, plan=False):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
@@ -1059,6 +1187,7 @@ class LiveSession:
         self.scan = _check_scan(scan, self.ground)
         self.localmap = _check_localmap(localmap, self.ground, self.ego)
         self.costmap = _check_costmap(costmap, self.localmap)
+        self.plan = _check_plan(plan, self.costmap, self.localmap)
         h, w = int(shape[0]), int(shape[1])
         if h <= 0 or w <= 0:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
@@ -1117,6 +1246,11 @@ class LiveSession:
             self._cost_par = dict(occ_level=self.localmap["occ_level"], free_level=self.localmap["free_level"],
                                   seed_r2=int(np.floor((cm["start_radius"] / self.localmap["cell"]) ** 2)),
                                   through_unknown=cm["through_unknown"])
+        if self.plan is not None:
+            pl = self.plan
+            self._plan_goal = pl["goal"]
+            self._plan_par = dict(goal_r2=int(np.floor((pl["goal_radius"] / self.localmap["cell"]) ** 2)), neutral=pl["neutral"],
+                                  factor=pl["factor"], unknown_cost=pl["unknown_cost"])
         self.src_shape = (h, w) if self.rect is None else self.rect.size  # the size of a frame as the camera hands it out
         # (rows, row_bytes, pitch, nbytes) of a source frame; ValueError if invalid
         self._layout = frame_layout(pixel_format, self.src_shape[0], self.src_shape[1], pitch)
@@ -1258,6 +1392,15 @@ class LiveSession:
                                 for _ in range(DEPTH)]
                 self._cost_lut = torch.from_numpy(self._cost_lut_host).to(dev)
                 self._cost_scratch = torch.empty(ops.cost_map_scratch(gh, gw, self._cost_R), dtype=torch.uint8, device=dev)
+            if self.plan is not None:
+                gh, gw = self.localmap["grid"]  # record, potential (the bits of a uint32), path[, dir]
+                self._d_plan = [torch.zeros(16, dtype=torch.float64, device=dev), torch.zeros(gh, gw, dtype=torch.int32, device=dev),
+                                torch.full((self.plan["max_path"],), -1, dtype=torch.int32, device=dev)]
+                if self.plan["dir"]:
+                    self._d_plan.append(torch.zeros(gh, gw, dtype=torch.uint8, device=dev))
+                self._h_plan = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_plan]
+                                for _ in range(DEPTH)]
+                self._plan_scratch = torch.empty(ops.plan_scratch(gh, gw), dtype=torch.uint8, device=dev)
             self._s_up, self._s_down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             ev = lambda: [torch.cuda.Event() for _ in range(DEPTH)]  # noqa: E731
             self._e_up, self._e_ingest, self._e_export, self._e_down = ev(), ev(), ev(), ev()
@@ -1358,6 +1501,12 @@ class LiveSession:
                     ops.cost_map(self._d_map[1], self._d_map[2], self._cost_lut, self._cost_R, self._cost_start, self._d_cost[1],
                                  self._d_cost[4] if self.costmap["nearest"] else None, self._d_cost[2], self._d_cost[3],
                                  self._d_cost[0], scratch=self._cost_scratch, **self._cost_par)
+                if self.plan is not None:  # (on the cost, reach and records the two calls above left on the device)
+                    goal = self._plan_goal
+                    ops.plan(self._d_cost[2], self._d_cost[3], self._cost_start, self._d_plan[1], self._d_plan[2], self._d_plan[0],
+                             dir=self._d_plan[3] if self.plan["dir"] else None,
+                             goal=goal if goal == "frontier" else ("world",) + goal, cost_record=self._d_cost[0],
+                             map_record=self._d_map[0], cell=self.localmap["cell"], scratch=self._plan_scratch, **self._plan_par)
             if self.tracks is not None:  # (after the ego fit it reads, before export_motion rolls the depth map)
                 with_ego = self.ego is not None and Ts is not None
                 ops.track_objects(Ts, self._depth_prev, self._K, self.shape, self._object_ids(), self._d_objects[0],
@@ -1409,6 +1558,9 @@ class LiveSession:
                 if self.costmap is not None:
                     for host, dev_buf in zip(self._h_cost[k], self._d_cost):
                         host.copy_(dev_buf, non_blocking=True)
+                if self.plan is not None:
+                    for host, dev_buf in zip(self._h_plan[k], self._d_plan):
+                        host.copy_(dev_buf, non_blocking=True)
                 self._e_down[k].record(self._s_down)
         self._inflight.append(k)
         self._pushed += 1
@@ -1449,6 +1601,10 @@ class LiveSession:
             hc = [t.numpy() for t in self._h_cost[k]]
             out.append(costmap_from_buffers(hc[0], hc[1], hc[2], hc[3], hc[4] if len(hc) > 4 else None, out[-1].origin,
                                             self.localmap["cell"], self._cost_start))
+        if self.plan is not None:
+            hp = [t.numpy() for t in self._h_plan[k]]
+            out.append(plan_from_buffers(hp[0], hp[1], hp[3] if len(hp) > 3 else None, hp[2], out[-1].origin,
+                                         self.localmap["cell"], self._cost_start))
         return out[0] if len(out) == 1 else tuple(out)
 
     def _object_ids(self):
@@ -1477,7 +1633,8 @@ class LiveSession:
         ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None; with ``egomotion``, an ``Ego`` or None
         follows; with ``confidence``, a ``Confidence``; with ``align_to``, an ``Aligned``; with ``epipolar``, an
         ``Epipolar``; with ``ground``, a ``Ground``; with ``objects``, an ``Objects``; with ``tracks``, a ``Tracks``; with
-        ``scan``, a ``Scan``; with ``localmap``, a ``LocalMap``; with ``costmap``, a ``CostMap`` comes last."""
+        ``scan``, a ``Scan``; with ``localmap``, a ``LocalMap``; with ``costmap``, a ``CostMap``; with ``plan``, a ``Plan``
+        comes last."""
         if self._ready:
             return self._ready.popleft()
         if not self._inflight:
@@ -1489,11 +1646,20 @@ class LiveSession:
         return len(self._ready) + len(self._inflight)
 
     def step(self, left_u8, right_u8):
-        """One frame, synchronously (any frames already pushed are returned first by ``pop``, so drain them before)."""
+        """One frame, synchronously (any frames already pushed are returned first by ``pop``, so drain them before): what
+        ``pop`` returns, a ``Plan`` last with ``plan``."""
         if self.pending():
             raise RuntimeError("step() on a session with frames in flight: pop() them first")
         self.push(left_u8, right_u8)
         return self.pop()
+
+    def set_goal(self, goal):
+        """The goal of ``plan`` for the frames pushed from now on: ``"frontier"`` or a point ``(x, z)`` of the map frame.
+        ValueError otherwise, and without ``plan=``.  No device call and no wait: the goal is an argument of the next
+        frame's ``codd_plan``."""
+        if self.plan is None:
+            raise ValueError("set_goal: the session has no plan=")
+        self._plan_goal = _check_goal(goal)
 
     def reset(self):
         """New sequence (reference reset_inference_state, model/codd.py:400-433).  Frames in flight stay poppable; the
@@ -1514,7 +1680,7 @@ class LiveSession:
                          "_d_objects", "_h_objects", "_objects_scratch", "_track_ids", "_d_tracks", "_h_tracks",
                          "_track_state", "_track_scratch", "_d_scan", "_h_scan", "_scan_edges", "_scan_scratch",
                          "_d_map", "_h_map", "_map_state", "_map_scratch", "_d_cost", "_h_cost", "_cost_lut",
-                         "_cost_scratch"):
+                         "_cost_scratch", "_d_plan", "_h_plan", "_plan_scratch"):
                 setattr(self, name, None)
             self._open_done = False
         self._inflight.clear()

@@ -2471,6 +2471,101 @@ def cost_map(map, age, lut, R, start, dist2, nearest, cost, reach, record, occ_l
     return record
 
 
+# CODD_PLAN_* of include/codd_hip.h: the potential of a cell no path leaves, the largest window, the goal modes
+PLAN_UNREACHED, PLAN_MAX_CELLS = 0xffffffff, 25600
+PLAN_GOAL_CELL, PLAN_GOAL_WORLD, PLAN_GOAL_FRONTIER = 0, 1, 2
+
+
+def _plan_shape_ok(gh, gw):
+    return gh >= 1 and gw >= 1 and gh * gw <= PLAN_MAX_CELLS
+
+
+def plan_scratch(gh, gw):
+    """Bytes of scratch ``plan`` needs (codd_plan_scratch)."""
+    n = int(_abi.load().codd_plan_scratch(int(gh), int(gw)))
+    if n <= 0:
+        raise ValueError(f"plan_scratch: gh, gw >= 1 and gh gw <= {PLAN_MAX_CELLS} expected, got {gh}, {gw}")
+    return n
+
+
+def plan_goal(goal):
+    """``goal`` of ``plan`` -> (mode, goal_i, goal_j, goal_x, goal_z): "frontier", ("cell", i, j) or ("world", x, z).
+    ValueError otherwise; no device call."""
+    if isinstance(goal, str) and goal == "frontier":
+        return PLAN_GOAL_FRONTIER, 0, 0, 0.0, 0.0
+    try:
+        kind, a, b = goal
+        if kind == "cell" and not isinstance(a, (bool, float)) and not isinstance(b, (bool, float)):
+            return PLAN_GOAL_CELL, int(a), int(b), 0.0, 0.0
+        if kind == "world" and not isinstance(a, bool) and not isinstance(b, bool):
+            return PLAN_GOAL_WORLD, 0, 0, float(a), float(b)
+    except (TypeError, ValueError):
+        pass
+    raise ValueError(f'plan: goal "frontier", ("cell", i, j) or ("world", x, z) expected, got {goal!r}')
+
+
+def plan(cost, reach, start, potential, path, record, *, dir=None, goal="frontier", cost_record=None, map_record=None,
+         cell=None, goal_r2=0, neutral=50, factor=205, unknown_cost=128, scratch=None):
+    """Which way do I go?  The navigation function and the path to a goal on one cost map (include/codd_hip.h, codd_plan).
+    ``cost`` and ``reach`` uint8 [gh,gw]: the outputs of ``cost_map``; ``start`` = (start_i, start_j) as given to it.
+    ``goal``: "frontier" (the nearest frontier: ``cost_record``, the record of ``cost_map``, is read on the device),
+    ("cell", i, j), or ("world", x, z) in the map frame (``map_record``, the record of ``local_map``, is read on the
+    device, and ``cell`` is the map's cell size).  ``goal_r2``: the squared radius in cells of the goal set.  A cell costs
+    ``neutral`` + ``factor`` c / 256 per unit of length, c its cost byte or ``unknown_cost`` for 255.  Outputs,
+    caller-owned device tensors: ``potential`` int32 [gh,gw] holding the uint32 bits (``PLAN_UNREACHED``: no path),
+    ``dir`` uint8 [gh,gw] or None, ``path`` int32 [max_path] (raster indices, -1 behind the last), ``record`` float64 [16].
+    ``scratch``: a uint8 tensor of ``plan_scratch`` bytes; allocated here when None.  ValueError for what the entry rejects,
+    before any device call.  One launch of one workgroup on the current stream, no host synchronisation."""
+    mode, goal_i, goal_j, goal_x, goal_z = plan_goal(goal)
+    if cost.dim() != 2:
+        raise ValueError("plan: cost [gh,gw] expected")
+    gh, gw = int(cost.shape[0]), int(cost.shape[1])
+    if not _plan_shape_ok(gh, gw):
+        raise ValueError(f"plan: gh, gw >= 1 and gh gw <= {PLAN_MAX_CELLS} expected, got {gh}, {gw}")
+    start_i, start_j = int(start[0]), int(start[1])
+    if not (0 <= start_i < gw and 0 <= start_j < gh):
+        raise ValueError(f"plan: start (i, j) inside the {gh} x {gw} window expected, got {tuple(start)!r}")
+    goal_r2, neutral, factor, unknown_cost = int(goal_r2), int(neutral), int(factor), int(unknown_cost)
+    if goal_r2 < 0 or goal_r2 >= 2 ** 31:
+        raise ValueError(f"plan: 0 <= goal_r2 < 2^31 expected, got {goal_r2}")
+    if not (1 <= neutral <= 255 and 0 <= factor <= 1024 and 0 <= unknown_cost <= 254):
+        raise ValueError(f"plan: neutral in [1, 255], factor in [0, 1024] and unknown_cost in [0, 254] expected, got {neutral}, "
+                         f"{factor}, {unknown_cost}")
+    if mode == PLAN_GOAL_CELL and not (0 <= goal_i < gw and 0 <= goal_j < gh):
+        raise ValueError(f"plan: a goal cell (i, j) inside the {gh} x {gw} window expected, got {goal_i}, {goal_j}")
+    if mode == PLAN_GOAL_FRONTIER and cost_record is None:
+        raise ValueError('plan: goal "frontier" reads cost_record, the record of cost_map')
+    c32 = 0.0
+    if mode == PLAN_GOAL_WORLD:
+        if map_record is None or cell is None:
+            raise ValueError('plan: a ("world", x, z) goal reads map_record, the record of local_map, and needs cell')
+        c32 = float(np.float32(cell))  # (the entry takes a float)
+        if not (np.isfinite([c32, goal_x, goal_z]).all() and c32 > 0 and abs(goal_x / c32) < 2 ** 30 and abs(goal_z / c32) < 2 ** 30):
+            raise ValueError(f"plan: finite cell > 0 and a finite goal with |goal / cell| < 2^30 expected, got {cell!r}, {goal_x!r}, "
+                             f"{goal_z!r}")
+    if path.dim() != 1 or path.numel() < 1 or path.numel() >= 2 ** 31:
+        raise ValueError("plan: path int32 [max_path] with max_path >= 1 expected")
+    lib = _abi.load()
+    _require_gpu(cost)
+    assert cost.dtype == torch.uint8 and cost.is_cuda and cost.is_contiguous()
+    assert reach.dtype == torch.uint8 and reach.is_cuda and reach.is_contiguous() and tuple(reach.shape) == (gh, gw)
+    assert potential.dtype == torch.int32 and potential.is_cuda and potential.is_contiguous() and tuple(potential.shape) == (gh, gw)
+    assert dir is None or (dir.dtype == torch.uint8 and dir.is_cuda and dir.is_contiguous() and tuple(dir.shape) == (gh, gw))
+    assert path.dtype == torch.int32 and path.is_cuda and path.is_contiguous()
+    for t in (record,) + tuple(r for r in (cost_record, map_record) if r is not None):
+        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.numel() == 16
+    if scratch is None:
+        scratch = torch.empty(plan_scratch(gh, gw), dtype=torch.uint8, device=cost.device)
+    assert scratch.dtype == torch.uint8 and scratch.is_cuda and scratch.is_contiguous()
+    _abi.check(lib.codd_plan(cost.data_ptr(), reach.data_ptr(),
+                             cost_record.data_ptr() if mode == PLAN_GOAL_FRONTIER else None,
+                             map_record.data_ptr() if mode == PLAN_GOAL_WORLD else None, gh, gw, start_i, start_j, mode, goal_i,
+                             goal_j, goal_x, goal_z, c32, goal_r2, neutral, factor, unknown_cost, int(path.numel()),
+                             scratch.data_ptr(), scratch.numel(), potential.data_ptr(), None if dir is None else dir.data_ptr(),
+                             path.data_ptr(), record.data_ptr(), _stream()), "plan")
+    return record
+
+
 ALIGN_MAX_FOOTPRINT = 4  # CODD_ALIGN_MAX_FOOTPRINT of include/codd_hip.h
 
 

@@ -1281,6 +1281,68 @@ int codd_cost_map(const short* map, const unsigned char* age, int gh, int gw, in
                   long long scratch_bytes, int* dist2, int* nearest, unsigned char* cost, unsigned char* reach,
                   double* record, void* stream);
 
+/* Live-session plan (codd_amd/live.py, plan=): what every user of a cost map computes next.  The navigation function -- the
+ * least cost to reach a goal from every cell the robot can reach -- and the path from the robot's cell to the goal, on the
+ * cost and reach codd_cost_map left on the device.  The goal is the nearest frontier (exploring), a cell, or a point of the
+ * map frame.  The reference has no such output; this replaces a download of cost and reach every frame and Dijkstra on the
+ * host.  Everything is an integer and everything below defines the result, not the algorithm: equal inputs give equal
+ * bytes.  No allocation, no host synchronisation, one launch of one workgroup whatever the data; every output element is
+ * rewritten on every call, inputs are never written.
+ * Inputs, DEVICE: cost uint8 [gh,gw] and reach uint8 [gh,gw], the outputs of codd_cost_map ([j,i]: row j, column i);
+ * cost_record, its 16 doubles, of which only [8] is read and only in FRONTIER mode (NULL otherwise is fine); map_record, the
+ * 16 doubles of codd_local_map, of which only [8:10] = ix0, iz0 are read and only in WORLD mode (NULL otherwise is fine).
+ * Host scalars: gh, gw; start_i, start_j, the ones given to codd_cost_map; mode, a CODD_PLAN_GOAL_*; goal_i, goal_j (CELL);
+ * goal_x, goal_z and cell (WORLD); goal_r2; neutral in [1, 255], factor in [0, 1024], unknown_cost in [0, 254]; max_path.
+ * gh gw <= CODD_PLAN_MAX_CELLS (the default 128 x 128, and 160 x 160: potential and weights of the whole window stay in the
+ * 160 KiB of LDS of one gfx950 CU); gh, gw >= 1 is the only limit on a side (a map of codd_local_map has sides of at most 4096).
+ * Domain.  D = the cells with reach != 0: by codd_cost_map's definition the 4-connected traversable component of the start
+ *   cell, empty when the start cell is not traversable.
+ * Weight.  c(q) = unknown_cost if cost[q] == CODD_COST_NO_INFO, else cost[q]; w(q) = neutral + (factor c(q)) / 256 (the
+ *   integer quotient), in [1, 1271]; 7 x 1271 x 25600 < 2^32, so a uint32 never overflows.
+ * Moves.  The eight neighbours k = 0 .. 7 with (di, dj) = (1,0), (-1,0), (0,1), (0,-1), (1,1), (-1,1), (1,-1), (-1,-1), of
+ *   length 5 for k < 4 and 7 otherwise.  A move p -> q is allowed iff p and q are in D and, for a diagonal one, (p.i + di,
+ *   p.j) and (p.i, p.j + dj) are in D too: no corner is cut, and every allowed diagonal can be replaced by two allowed
+ *   straight moves.
+ * Goal cell (gj, gi).  CODD_PLAN_GOAL_CELL: goal_i, goal_j.  CODD_PLAN_GOAL_WORLD: gi = (long long)floor(goal_x /
+ *   (double)cell) - (long long)map_record[8], gj likewise from goal_z and [9], each clamped into the window; CLAMPED = 1 iff
+ *   either changed (the usual projection of a global goal onto a local window).  CODD_PLAN_GOAL_FRONTIER: r = (long
+ *   long)cost_record[8]; no goal cell if r < 0, else (gj, gi) = (r / gw, r % gw).
+ * Goal set G = the cells of D with (i - gi)^2 + (j - gj)^2 <= goal_r2.  If that set is empty, a goal cell exists and D is
+ *   not empty, G is the single cell of D nearest to the goal cell -- by that squared distance, ties to the smallest raster
+ *   index -- and SNAPPED = 1.  Without a goal cell, or with D empty, G is empty.
+ * potential uint32 [gh,gw]: P(p) = 0 on G; elsewhere in D, P(p) = the minimum over the allowed moves p -> q of len w(q) +
+ *   P(q): the least sum of len w over the cells ENTERED, over all paths of allowed moves from p into G (w >= 1: exactly
+ *   one solution; with G not empty it is finite exactly on D); CODD_PLAN_UNREACHED outside D, and everywhere when G is empty.
+ * dir uint8 [gh,gw], or NULL: 8 on G; on the other cells with finite P the smallest k whose move is allowed and attains
+ *   P(p); 255 elsewhere.
+ * path int32 [max_path]: if P at the start cell is finite, the raster index of the start cell, then the cells dir leads
+ *   through up to and including the first cell of G; at most max_path entries, -1 behind them.  P decreases strictly along
+ *   it, so it has at most gh gw cells.
+ * record, 16 doubles, never NaN: [0] FOUND (P at the start cell is finite), [1] P there (-1), [2] the cells of the full
+ *   path, also when it was truncated (0), [3] the entries written = min([2], max_path), [4] the goal cell's raster index
+ *   after clamping (-1 for none), [5] CLAMPED, [6] SNAPPED, [7] the cells of G, [8] the raster index of the path's last
+ *   cell, which is in G (-1), [9] the cells with finite P, [10] the largest finite P (-1 for none), [11] the largest cost byte
+ *   other than 255 over the cells of the full path (-1 if not found or no such cell: how close to obstacles the path runs),
+ *   [12] the path's length in units of 5 and 7 (the sum of len), [13:16] zero.  Nothing that depends on the algorithm is in
+ *   it.
+ * scratch: codd_plan_scratch(gh, gw) bytes (-1 for a shape outside the limits): the alignment and a few counters, contents
+ * irrelevant, any alignment.  potential and path need the alignment of an int32, the records that of a double.
+ * CODD_EINVAL, before any launch: cost, reach, potential, path, record or scratch NULL (dir may be); the record the mode
+ * reads NULL; the shape outside the limits; start_i outside [0, gw) or start_j outside [0, gh); an unknown mode; in CELL mode
+ * goal_i outside [0, gw) or goal_j outside [0, gh); goal_r2 < 0; max_path < 1; neutral, factor or unknown_cost outside
+ * their ranges; in WORLD mode cell, goal_x or goal_z not finite, cell <= 0, or |goal / cell| >= 2^30; scratch_bytes below
+ * the size function's answer. */
+#define CODD_PLAN_MAX_CELLS 25600
+#define CODD_PLAN_UNREACHED 0xffffffffu
+#define CODD_PLAN_GOAL_CELL 0
+#define CODD_PLAN_GOAL_WORLD 1
+#define CODD_PLAN_GOAL_FRONTIER 2
+long long codd_plan_scratch(int gh, int gw);
+int codd_plan(const unsigned char* cost, const unsigned char* reach, const double* cost_record, const double* map_record,
+              int gh, int gw, int start_i, int start_j, int mode, int goal_i, int goal_j, double goal_x, double goal_z,
+              float cell, int goal_r2, int neutral, int factor, int unknown_cost, int max_path, void* scratch,
+              long long scratch_bytes, unsigned* potential, unsigned char* dir, int* path, double* record, void* stream);
+
 /* Ablation plug-ins.  codd_fusion_select: mode 0 = KalmanFusion (model/fusion/others.py:124-153; constant
  * gain K = Q/(Q+R), the reference never updates P), mode 1 = GTFusion (:54-86; gt [B,1,hg,wg], zero-padded).
  * cur, warp, out: [B,1,H,W]. */
