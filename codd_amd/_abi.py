@@ -162,6 +162,9 @@ SIGNATURES = {
     "codd_local_map_scratch": (_ll, [_i, _i]),
     "codd_local_map": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _i, _i, _i, _f, _f, _f, C.c_uint, _i, _i, _i, _i, _i,
                             _i, _i, _i, _i, _p, _p, _p, _p, _ll, _p, _p, _p, _p]),
+    "codd_height_map_scratch": (_ll, [_i, _i]),
+    "codd_height_map": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _i, _i, _f, _f, _f, _f, C.c_uint, _i, _i, _i, _i, _i,
+                             _p, _p, _p, _p, _p, _ll, _p, _p, _p, _p, _p, _p, _p, _p]),
     "codd_cost_map_scratch": (_ll, [_i, _i, _i]),
     "codd_cost_map": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _p, _ll, _p, _p, _p, _p, _p, _p]),
     "codd_plan_scratch": (_ll, [_i, _i]),

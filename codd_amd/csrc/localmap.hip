@@ -23,18 +23,7 @@
 #pragma clang fp contract(off)  // every operation of the contract rounds once
 
 #include "floor_frame.h"  // ScanFrame, scan_frame, scan_ground: the ground frame of codd_objects' "per pixel" paragraph
-
-#define MAP_BW 8   // a wave's block: MAP_BW x MAP_BW pixels
-#define MAP_TW 32  // a workgroup's tile: four blocks side by side
-#define MAP_MAX_SIDE 4096
-#define MAP_MAX_CELLS (1 << 22)
-
-// the state's 32 doubles (include/codd_hip.h)
-enum {
-  ST_EXISTS = 0, ST_PX = 1, ST_PZ = 2, ST_HX = 3, ST_HZ = 4, ST_IX0 = 5, ST_IZ0 = 6, ST_FRAMES = 7, ST_RESTARTS = 8,
-  ST_N = 9, ST_HC = 12, ST_F = 13, ST_PIX0 = 16, ST_PIZ0 = 17, ST_CLEARED = 18, ST_INTEGRATED = 19, ST_LINKED = 20,
-  ST_DX = 21, ST_DZ = 22
-};
+#include "map_window.h"   // the state's slots, the limits, map_mod, map_pixel_cell: shared with the layers on this window
 
 struct MapArgs {
   const float* disp;
@@ -54,11 +43,6 @@ struct MapArgs {
   int W, h, w, gh, gw, min_pixels, l_occ, l_free, l_min, l_max, decay, occ_level, free_level, lost, fresh;
   float fx, fy, cx, cy, calib, cell, range_min, range_max;
 };
-
-__device__ __forceinline__ int map_mod(long long v, int n) {
-  const int m = (int)(v % n);
-  return m < 0 ? m + n : m;
-}
 
 // ---- 1: the pose
 __global__ __launch_bounds__(64) void map_pose_kernel(MapArgs a) {
@@ -199,16 +183,8 @@ __global__ __launch_bounds__(256) void map_pixel_kernel(MapArgs a) {
       const ScanFrame g = scan_frame(a.rec);
       float gx, gz;
       scan_ground(a, g, y, x, d, &gx, &gz);
-      const float rho = sqrtf((gx * gx) + (gz * gz));
-      if (rho >= a.range_min && rho < a.range_max) {
-        const double cell = (double)a.cell;
-        const float oxf = (float)(st[ST_PX] - st[ST_IX0] * cell), ozf = (float)(st[ST_PZ] - st[ST_IZ0] * cell);
-        const float hxf = (float)st[ST_HX], hzf = (float)st[ST_HZ];
-        const float wx = (gx * hzf + gz * hxf) + oxf, wz = (gz * hzf - gx * hxf) + ozf;
-        const float jx = floorf(wx / a.cell), jz = floorf(wz / a.cell);
-        if (jx >= 0.f && jx < (float)a.gw && jz >= 0.f && jz < (float)a.gh)  // (NaN is outside)
-          key = 2 * ((int)jz * a.gw + (int)jx) + (obst ? 1 : 0);
-      }
+      int jz, jx;
+      if (map_pixel_cell(a, st, gx, gz, &jz, &jx)) key = 2 * (jz * a.gw + jx) + (obst ? 1 : 0);
     }
   }
 #ifdef LOCALMAP_LANE_ATOMICS
@@ -286,10 +262,6 @@ __global__ __launch_bounds__(256) void map_update_kernel(MapArgs a) {
 }
 
 // ---- the scratch: O, F, the counters; 16-byte aligned by the call itself
-static inline bool map_shape_ok(int gh, int gw) {
-  return gh >= 1 && gh <= MAP_MAX_SIDE && gw >= 1 && gw <= MAP_MAX_SIDE && (long long)gh * gw <= MAP_MAX_CELLS;
-}
-
 extern "C" long long codd_local_map_scratch(int gh, int gw) {
   if (!map_shape_ok(gh, gw)) return -1;
   return 16 + 8LL * gh * gw + 32;

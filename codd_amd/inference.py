@@ -116,6 +116,13 @@ def parse_args(argv=None):
                         "length float64 [1, frames], start (i, j) and cell")
     p.add_argument("--plan-goal", default="frontier", metavar="frontier|X,Z",
                    help="--plan: the nearest frontier (default) or a point X,Z of the map frame")
+    p.add_argument("--heightmap", action="store_true",
+                   help="--localmap: a rolling elevation layer on the local map's cells, kept across the frames; also write "
+                        "<name>.heightmap.pred.npz: top, bot and ceil int16 [1, frames, gh, gw] in units of h_res above the "
+                        "floor (-32768: no surface, 32767: no overhead), age uint8 (255: never seen), step uint16 and flags "
+                        "uint8 [1, frames, gh, gw] (1 step, 2 headroom, 4 hole; 255: unknown), integrated, surface_pixels, "
+                        "overhead_pixels, observed, known, steps, headroom and holes int32 [1, frames], origin int64 [1, frames, "
+                        "2], cell and h_res")
     p.add_argument("--align-footprint", type=int, default=None, choices=[1, 2, 3, 4],
                    help="--align: target pixels per source pixel and axis (default: the smallest that leaves no hole lines)")
     p.add_argument("--rectify-maps", help="--live: .npz with left_x, left_y, right_x, right_y (fp32 [h,w]) applied on the GPU")
@@ -181,6 +188,8 @@ def parse_args(argv=None):
         p.error("--costmap needs --localmap")
     if args.plan and not args.costmap:
         p.error("--plan needs --costmap")
+    if args.heightmap and not args.localmap:
+        p.error("--heightmap needs --localmap")
     if args.plan_goal != "frontier":
         m = re.fullmatch(r"([^,]+),([^,]+)", args.plan_goal)
         try:
@@ -367,7 +376,8 @@ def run_live(args, model, videos):
     (per-frame ranges, free ranges, objects and counts, written with or without --show) and, with --localmap,
     <name>.localmap.pred.npz (per-frame map, age plane, pose and counts, written with or without --show) and, with --costmap,
     <name>.costmap.pred.npz (per-frame cost, dist2, reach, counts and nearest frontier, likewise) and, with --plan,
-    <name>.plan.pred.npz (per-frame potential, path and counts, likewise).  With --pixel-format the
+    <name>.plan.pred.npz (per-frame potential, path and counts, likewise) and, with --heightmap,
+    <name>.heightmap.pred.npz (per-frame elevation layers, flags and counts, likewise).  With --pixel-format the
     frame files are raw byte dumps of --frame-size in that camera format (iter_raw_frames) and are decoded on the GPU.  With
     --calibration the frames (files or --frame-size) have the calibration's source size and every result has --net-size."""
     from PIL import Image
@@ -403,6 +413,8 @@ def run_live(args, model, videos):
         extra["costmap"] = True
     if getattr(args, "plan", False):
         extra["plan"] = dict(goal=getattr(args, "plan_goal", "frontier"))
+    if getattr(args, "heightmap", False):
+        extra["heightmap"] = True
     raw = getattr(args, "pixel_format", None)
     if raw:
         extra.update(pixel_format=raw, pitch=args.pitch, yuv=args.yuv or "bt601")
@@ -443,10 +455,14 @@ def run_live(args, model, videos):
                 aligned = _NpzStream(osp.join(args.show_dir, name + ".aligned.pred.npz"), "depth",
                                      (1, nf) + s.align_target.camera.size, np.float32)
         n, epis, grounds, objs, trks, scans, maps, costs, plans = 0, [], [], [], [], [], [], [], []
+        heights = []
         try:
             frames = iter_raw_frames(lefts, rights, raw, src, args.pitch) if raw else iter_frames(lefts, rights)
             for res in live_results(s, frames):
                 n += 1
+                if "heightmap" in extra:
+                    res, hm = res[:-1], res[-1]  # (a LocalMap precedes it: still a tuple)
+                    heights.append(hm)
                 if "plan" in extra:
                     res, pl = res[:-1], res[-1]  # (a CostMap precedes it: still a tuple)
                     plans.append(pl)
@@ -631,6 +647,21 @@ def run_live(args, model, videos):
                   f"{len(found)} of {len(plans)} frames"
                   + (f", the last {found[-1].length:.3f} long over {found[-1].length_cells} cells at cost {found[-1].cost}, at most "
                      f"cost {found[-1].max_cost_on_path} on it, {found[-1].reached} cells reached" if found else ""))
+        if "heightmap" in extra:
+            os.makedirs(args.show_dir, exist_ok=True)
+            np.savez(osp.join(args.show_dir, name + ".heightmap.pred.npz"),
+                     top=np.array([[hm.top_q for hm in heights]], np.int16), bot=np.array([[hm.bot_q for hm in heights]], np.int16),
+                     ceil=np.array([[hm.ceil_q for hm in heights]], np.int16), age=np.array([[hm.age for hm in heights]], np.uint8),
+                     step=np.array([[hm.step for hm in heights]], np.uint16), flags=np.array([[hm.flags for hm in heights]], np.uint8),
+                     origin=np.array([[hm.origin for hm in heights]], np.int64).reshape(1, len(heights), 2),
+                     **{k: np.array([[int(getattr(hm, k)) for hm in heights]], np.int32)
+                        for k in ("integrated", "surface_pixels", "overhead_pixels", "observed", "known", "steps", "headroom",
+                                  "holes")},
+                     cell=np.array(s.localmap["cell"], np.float64), h_res=np.array(s.heightmap["h_res"], np.float64))
+            print(f"{name}: heightmap: {sum(hm.integrated for hm in heights)} integrated in {len(heights)} frames"
+                  + (f", {heights[-1].known} known cells at the end: {heights[-1].steps} steps, {heights[-1].headroom} without "
+                     f"headroom, {heights[-1].holes} holes, top up to {heights[-1].top_max:.3f}, bot down to "
+                     f"{heights[-1].bot_min:.3f}" if heights else ""))
         print(f"{name}: {n} frames")
     for s in sessions.values():
         s.close()

@@ -84,6 +84,10 @@ With ``plan=`` (which needs ``costmap=``) the session says which way to go: ``co
 ``codd_cost_map`` on the cost and reach it left on the device and returns the navigation function -- the least cost to reach
 the goal from every reachable cell -- and the path from the camera's cell to the goal.  The goal is the nearest frontier
 (exploring) or a point of the map frame, changed between frames with ``set_goal``.  Integers only, one launch.
+
+With ``heightmap=`` (which needs ``localmap=``) the session also says how high things are: ``codd_height_map`` runs right
+behind ``codd_local_map`` on the pose and window it left and keeps a 2.5-D elevation layer on the map's cells -- the highest
+and lowest surface and the lowest overhead thing per cell, with step, headroom and hole flags.  Integers only, 4 launches.
 """
 from collections import deque, namedtuple
 
@@ -125,6 +129,10 @@ COSTMAP_DEFAULTS = dict(robot_radius=0.3, inflation_radius=1.0, scaling=3.0, sta
 # nearest frontier, which is what a robot without orders does; 1024 path cells cover the diagonal of the default window
 # more than five times.
 PLAN_DEFAULTS = dict(goal="frontier", goal_radius=0.0, neutral=50, factor=205, unknown_cost=128, max_path=1024, dir=False)
+# Chosen by reasoning, not measured on real footage (ops.HEIGHT_PARAMS says why): 5 mm units, every surface label, four
+# pixels as the map's, half way to each new observation, a platform that climbs and drops 10 cm and stands 1 m tall.
+HEIGHTMAP_DEFAULTS = dict(h_res=0.005, select=("floor", "obstacle", "below"), min_pixels=4, alpha=128, max_step=0.10,
+                          robot_height=1.0, max_drop=0.10)
 OBJECT_LABELS = dict(floor=ops.GROUND_FLOOR, obstacle=ops.GROUND_OBSTACLE, overhead=ops.GROUND_OVERHEAD,
                      below=ops.GROUND_BELOW)  # the names ``select`` takes
 
@@ -400,6 +408,51 @@ def plan_from_buffers(record, potential, dir, path, origin, cell, start):
                 bool(r[0] != 0), int(r[1]), int(r[2]), bool(r[2] > r[3]), at(r[4]), bool(r[5] != 0), bool(r[6] != 0), at(r[8]),
                 int(r[9]), int(r[11]), float(r[12]) * float(cell) / 5.0, (int(origin[0]), int(origin[1])), float(cell),
                 (int(start[0]), int(start[1])))
+
+
+# One frame's view of the rolling elevation layer, caller-owned; [j,i] is the LocalMap's cell [j,i].  top, bot and ceil fp32
+# [gh,gw]: the highest and the lowest surface seen in the cell and the lowest thing hanging over it, in the unit of
+# calib / fx above the floor plane of the frame that saw them (not a global datum), NaN where nothing was seen; top_q, bot_q
+# and ceil_q int16 [gh,gw]: the same in units of h_res as the device keeps them (ops.HEIGHT_NONE -32768: no surface,
+# ops.HEIGHT_NO_CEIL 32767: no overhead); age uint8 [gh,gw]: 255 never observed inside the window, otherwise frames since the
+# last observation (254: that or more); step uint16 [gh,gw]: how far the cell's top stands above its lowest known
+# 8-neighbour, in units of h_res; flags uint8 [gh,gw]: ops.HEIGHT_UNKNOWN 255 for a cell without a surface, otherwise the
+# bits ops.HEIGHT_STEP (step > max_step), ops.HEIGHT_HEADROOM (ceil - top < robot_height), ops.HEIGHT_HOLE (bot < -max_drop);
+# integrated: the frame's pixels were added; surface_pixels and overhead_pixels: the pixels added; observed: cells
+# updated by this frame; known: cells with a surface; steps, headroom, holes: cells with each flag; top_max and bot_min:
+# the largest top and the smallest bot over the known cells, in the layer's unit (0.0 without one); origin and cell as the
+# LocalMap's; h_res.
+_HeightMap = namedtuple("HeightMap", "top bot ceil top_q bot_q ceil_q age step flags integrated surface_pixels overhead_pixels "
+                                     "observed known steps headroom holes top_max bot_min origin cell h_res")
+
+
+class HeightMap(_HeightMap):
+    __slots__ = ()
+
+    world_xz = LocalMap.world_xz  # (the same cells: it reads ``origin`` and ``cell`` alone)
+
+    def traversable(self):
+        """bool [gh,gw]: ``flags == 0`` -- a known cell without a step, with headroom and without a hole."""
+        return self.flags == 0
+
+
+def heightmap_from_buffers(record, top, bot, ceil, age, step, flags, cell, h_res):
+    """record float64 [16], top_out, bot_out, ceil_out int16, hage_out uint8, step_out uint16 and flags_out uint8 [gh,gw] of
+    codd_height_map (include/codd_hip.h), the LocalMap's ``cell`` and ``h_res`` -> ``HeightMap`` (copies: the buffers may be
+    reused)."""
+    r = np.asarray(record, np.float64)
+    res = np.float32(h_res)
+    tq, bq, cq = (np.array(v, np.int16) for v in (top, bot, ceil))
+
+    def metres(q, none):
+        out = q.astype(np.float32) * res
+        out[q == none] = np.nan
+        return out
+
+    return HeightMap(metres(tq, ops.HEIGHT_NONE), metres(bq, ops.HEIGHT_NONE), metres(cq, ops.HEIGHT_NO_CEIL), tq, bq, cq,
+                     np.array(age, np.uint8), np.array(np.asarray(step).view(np.uint16)), np.array(flags, np.uint8), bool(r[0] != 0),
+                     int(r[1]), int(r[2]), int(r[3]), int(r[4]), int(r[5]), int(r[6]), int(r[7]), float(r[8]) * float(h_res),
+                     float(r[9]) * float(h_res), (int(r[10]), int(r[11])), float(cell), float(h_res))
 
 
 def _unit_up(up, pitch_deg=0.0):
@@ -898,6 +951,48 @@ def _check_plan(plan, costmap=True, localmap=True):
     return p
 
 
+def _check_heightmap(heightmap, localmap=True):
+    """False / None -> None; True -> the defaults; a dict overrides them.  ``localmap``: the checked ``localmap`` dict.
+    ValueError otherwise, and for ``heightmap`` without ``localmap`` (no device call)."""
+    if heightmap is None or heightmap is False:
+        return None
+    if not (heightmap is True or isinstance(heightmap, dict)):
+        raise ValueError(f"heightmap: False, True or a dict of {tuple(HEIGHTMAP_DEFAULTS)} expected, got {heightmap!r}")
+    if localmap is None or localmap is False:
+        raise ValueError("heightmap: needs localmap= (the layer lives on the local map's window and reads its pose)")
+    unknown = set(heightmap) - set(HEIGHTMAP_DEFAULTS) if isinstance(heightmap, dict) else ()
+    if unknown:
+        raise ValueError(f"heightmap: unknown keys {sorted(unknown)}; known: {tuple(HEIGHTMAP_DEFAULTS)}")
+    p = dict(HEIGHTMAP_DEFAULTS, **(heightmap if isinstance(heightmap, dict) else {}))
+    for k in ("h_res", "max_step", "robot_height", "max_drop"):
+        try:
+            if isinstance(p[k], (bool, np.bool_)):
+                raise TypeError
+            p[k] = float(p[k])
+        except (TypeError, ValueError):
+            raise ValueError(f"heightmap: a number expected for {k}, got {p[k]!r}") from None
+        if not np.isfinite(p[k]):
+            raise ValueError(f"heightmap: a finite {k} expected, got {p[k]!r}")
+    if not p["h_res"] > 0:
+        raise ValueError(f"heightmap: positive h_res expected, got {p['h_res']!r}")
+    for k in ("max_step", "robot_height", "max_drop"):
+        if not 0 <= np.rint(p[k] / p["h_res"]) <= ops.HEIGHT_Q_MAX:
+            raise ValueError(f"heightmap: 0 <= {k} / h_res <= {ops.HEIGHT_Q_MAX} expected, got {p[k]!r} / {p['h_res']!r}")
+    for k, lo_, hi_ in (("min_pixels", 1, 2 ** 31 - 1), ("alpha", 1, 256)):
+        if isinstance(p[k], (bool, np.bool_)) or not isinstance(p[k], (int, np.integer)) or not lo_ <= p[k] <= hi_:
+            raise ValueError(f"heightmap: an integer {k} in [{lo_}, {hi_}] expected, got {p[k]!r}")
+        p[k] = int(p[k])
+    sel = p["select"]
+    if isinstance(sel, str):
+        sel = (sel,)
+    if not (isinstance(sel, (tuple, list)) and all(isinstance(v, str) and v in OBJECT_LABELS for v in sel)):
+        raise ValueError(f"heightmap: select: names of {tuple(OBJECT_LABELS)} expected, got {p['select']!r}")
+    if "overhead" in sel:
+        raise ValueError("heightmap: select: overhead pixels go to the ceil layer, they are not a surface")
+    p["select"] = tuple(sel)
+    return p
+
+
 def scan_span(p, K, w):
     """(angle_min, angle_max) in radians of the checked ``scan`` dict: ``angles_deg``, or the camera's own horizontal field
     atan((0 - cx) / fx) .. atan((w - 1 - cx) / fx)."""
@@ -1043,7 +1138,7 @@ class LiveSession:
     ``egomotion`` (False, True, or a dict overriding ``iters``, ``delta_px``, ``tau_px``, ``min_valid``): ``pop`` and
     ``step`` also return an ``Ego`` (or None for a frame without a field).  The tuple order is fixed:
     ``result[, motion][, ego][, confidence][, aligned][, epipolar][, ground][, objects][, tracks][, scan][, localmap]
-    [, costmap][, plan]``, each part present iff requested.
+    [, costmap][, plan][, heightmap]``, each part present iff requested.
 
     ``confidence`` (False, True, or a dict overriding ``occ_px`` (1.0 pixel) and ``tau`` (24.0 grey levels)): ``pop`` and
     ``step`` also return a ``Confidence(flags, residual)`` on the CURRENT frame's grid, for every frame (never None).  It
@@ -1163,13 +1258,25 @@ class LiveSession:
     (diagonal) into a cell costing ``neutral`` + ``factor`` cost / 256 (``unknown_cost`` for cost 255); ``path`` the cells
     from the camera's cell to the goal, at most ``max_path``; ``dir`` also returns the move to make at every cell.  The
     defaults are navfn's and are reasoned, not measured on real footage.  Defined in include/codd_hip.h (codd_plan).
+
+    ``heightmap`` (False, True, or a dict overriding ``HEIGHTMAP_DEFAULTS``; needs ``localmap``, ValueError without it and
+    for ``"overhead"`` in ``select``): ``pop`` and ``step`` also return a ``HeightMap`` on the frame's ``LocalMap`` cells,
+    for every frame (never None), last in the tuple, after the ``Plan``.  ``codd_height_map`` runs right behind
+    ``codd_local_map`` and keeps, per cell and across frames, the highest and the lowest surface seen (``top``, ``bot``)
+    and the lowest overhead thing (``ceil``) in units of ``h_res`` above the floor plane of the frame that saw them: a
+    blend ``alpha`` / 256 of the way to each frame's extreme over the pixels of the ``select`` labels (overhead pixels
+    for ``ceil``), for cells with at least ``min_pixels`` of them.  ``flags`` marks the upper cell of a step above
+    ``max_step``, a cell with less than ``robot_height`` between ``top`` and ``ceil``, and a cell whose ``bot`` lies more
+    than ``max_drop`` below the floor; ``traversable()`` is ``flags == 0``.  The layers restart with the map (``reset``, a
+    LOST frame under ``lost="reset"``).  The defaults are reasoned, not measured on real footage.  Defined in
+    include/codd_hip.h (codd_height_map).
     """
 
     def __init__(self, estimator, shape, intrinsics=None, calib=None, output="depth",
                  bgr=False, rectify=None, use_graph=True, divisor=64, motion=None, egomotion=False, confidence=False,
                  pixel_format="rgb8", yuv="bt601", pitch=None, calibration=None, zoom=1.0, align_to=None, align=None,
                  epipolar=False, ground=False, objects=False, tracks=False, scan=False, localmap=False,
-                 costmap=False, plan=False):
+                 costmap=False, plan=False, heightmap=False):
         if output not in OUTPUTS:
             raise ValueError(f"output: one of {OUTPUTS} expected, got {output!r}")
         if motion is not None and motion not in MOTIONS:
@@ -1188,6 +1295,7 @@ class LiveSession:
         self.localmap = _check_localmap(localmap, self.ground, self.ego)
         self.costmap = _check_costmap(costmap, self.localmap)
         self.plan = _check_plan(plan, self.costmap, self.localmap)
+        self.heightmap = _check_heightmap(heightmap, self.localmap)
         h, w = int(shape[0]), int(shape[1])
         if h <= 0 or w <= 0:
             raise ValueError(f"shape: positive (h, w) expected, got {shape}")
@@ -1251,6 +1359,10 @@ class LiveSession:
             self._plan_goal = pl["goal"]
             self._plan_par = dict(goal_r2=int(np.floor((pl["goal_radius"] / self.localmap["cell"]) ** 2)), neutral=pl["neutral"],
                                   factor=pl["factor"], unknown_cost=pl["unknown_cost"])
+        if self.heightmap is not None:
+            hm = self.heightmap
+            self._height_par = dict({k: hm[k] for k in ops.HEIGHT_PARAMS if k != "select"}, select=select_mask(hm["select"]),
+                                    **{k: self.localmap[k] for k in ("cell", "range_min", "range_max")})
         self.src_shape = (h, w) if self.rect is None else self.rect.size  # the size of a frame as the camera hands it out
         # (rows, row_bytes, pitch, nbytes) of a source frame; ValueError if invalid
         self._layout = frame_layout(pixel_format, self.src_shape[0], self.src_shape[1], pitch)
@@ -1401,6 +1513,16 @@ class LiveSession:
                 self._h_plan = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_plan]
                                 for _ in range(DEPTH)]
                 self._plan_scratch = torch.empty(ops.plan_scratch(gh, gw), dtype=torch.uint8, device=dev)
+            if self.heightmap is not None:
+                gh, gw = self.localmap["grid"]  # record, top_out, bot_out, ceil_out, hage_out, step_out, flags_out
+                i16, u8 = torch.int16, torch.uint8
+                self._d_height = [torch.zeros(16, dtype=torch.float64, device=dev)] + [
+                    torch.zeros(gh, gw, dtype=dt, device=dev) for dt in (i16, i16, i16, u8, torch.uint16, u8)]
+                self._h_height = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in self._d_height]
+                                  for _ in range(DEPTH)]
+                # top, bot, ceil, hage: the map's first call is CLEARED and gives every cell its sentinels
+                self._height_state = [torch.zeros(gh, gw, dtype=dt, device=dev) for dt in (i16, i16, i16, u8)]
+                self._height_scratch = torch.empty(ops.height_map_scratch(gh, gw), dtype=torch.uint8, device=dev)
             self._s_up, self._s_down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             ev = lambda: [torch.cuda.Event() for _ in range(DEPTH)]  # noqa: E731
             self._e_up, self._e_ingest, self._e_export, self._e_down = ev(), ev(), ev(), ev()
@@ -1497,6 +1619,10 @@ class LiveSession:
                               self._d_ego[0] if Ts is not None else None, *self._map_state, self._d_map[1], self._d_map[2],
                               self._d_map[0], fresh=self._map_fresh, scratch=self._map_scratch, **self._map_par)
                 self._map_fresh = False
+                if self.heightmap is not None:  # (right behind the map: it reads the pose and the window that call left)
+                    ops.height_map(disp, self._epi_K, self.calib, self.shape, self._d_ground[1], self._d_ground[0],
+                                   self._map_state[0], *self._height_state, *self._d_height[1:], self._d_height[0],
+                                   scratch=self._height_scratch, **self._height_par)
                 if self.costmap is not None:  # (on the unrolled map and age plane the call above left on the device)
                     ops.cost_map(self._d_map[1], self._d_map[2], self._cost_lut, self._cost_R, self._cost_start, self._d_cost[1],
                                  self._d_cost[4] if self.costmap["nearest"] else None, self._d_cost[2], self._d_cost[3],
@@ -1561,6 +1687,9 @@ class LiveSession:
                 if self.plan is not None:
                     for host, dev_buf in zip(self._h_plan[k], self._d_plan):
                         host.copy_(dev_buf, non_blocking=True)
+                if self.heightmap is not None:
+                    for host, dev_buf in zip(self._h_height[k], self._d_height):
+                        host.copy_(dev_buf, non_blocking=True)
                 self._e_down[k].record(self._s_down)
         self._inflight.append(k)
         self._pushed += 1
@@ -1605,6 +1734,9 @@ class LiveSession:
             hp = [t.numpy() for t in self._h_plan[k]]
             out.append(plan_from_buffers(hp[0], hp[1], hp[3] if len(hp) > 3 else None, hp[2], out[-1].origin,
                                          self.localmap["cell"], self._cost_start))
+        if self.heightmap is not None:  # (last: the cost map and the plan index out[-1] above)
+            out.append(heightmap_from_buffers(*(t.numpy() for t in self._h_height[k]), self.localmap["cell"],
+                                              self.heightmap["h_res"]))
         return out[0] if len(out) == 1 else tuple(out)
 
     def _object_ids(self):
@@ -1633,8 +1765,8 @@ class LiveSession:
         ``motion`` mode, ``(result, motion)`` with motion fp32 [h,w,C] or None; with ``egomotion``, an ``Ego`` or None
         follows; with ``confidence``, a ``Confidence``; with ``align_to``, an ``Aligned``; with ``epipolar``, an
         ``Epipolar``; with ``ground``, a ``Ground``; with ``objects``, an ``Objects``; with ``tracks``, a ``Tracks``; with
-        ``scan``, a ``Scan``; with ``localmap``, a ``LocalMap``; with ``costmap``, a ``CostMap``; with ``plan``, a ``Plan``
-        comes last."""
+        ``scan``, a ``Scan``; with ``localmap``, a ``LocalMap``; with ``costmap``, a ``CostMap``; with ``plan``, a ``Plan``;
+        with ``heightmap``, a ``HeightMap`` comes last."""
         if self._ready:
             return self._ready.popleft()
         if not self._inflight:
@@ -1680,7 +1812,8 @@ class LiveSession:
                          "_d_objects", "_h_objects", "_objects_scratch", "_track_ids", "_d_tracks", "_h_tracks",
                          "_track_state", "_track_scratch", "_d_scan", "_h_scan", "_scan_edges", "_scan_scratch",
                          "_d_map", "_h_map", "_map_state", "_map_scratch", "_d_cost", "_h_cost", "_cost_lut",
-                         "_cost_scratch", "_d_plan", "_h_plan", "_plan_scratch"):
+                         "_cost_scratch", "_d_plan", "_h_plan", "_plan_scratch", "_d_height", "_h_height", "_height_state",
+                         "_height_scratch"):
                 setattr(self, name, None)
             self._open_done = False
         self._inflight.clear()

@@ -1229,6 +1229,87 @@ int codd_local_map(const float* disp, int H, int W, int h, int w, float fx, floa
                    short* logodds, unsigned char* age, void* scratch, long long scratch_bytes, short* map_out,
                    unsigned char* age_out, double* record, void* stream);
 
+/* Live-session elevation layer (codd_amd/live.py, heightmap=): how high is it, and do I fit?  A rolling 2.5-D layer
+ * registered cell for cell to codd_local_map's window -- the same gh x gw, cell, origin and toroidal addressing --
+ * integrated from the same pixels by the same floor-frame expressions and kept across frames: per cell the highest and the
+ * lowest surface seen and the lowest thing hanging over it, so that a kerb differs from a wall, a pit is a pit and a beam is
+ * remembered after it has left the view.  The reference has no such output; this replaces downloading labels, disparity and
+ * the height map every frame and rasterising every pixel on the host.  4 launches, no allocation, no host synchronisation,
+ * no launch count or grid that depends on the data, integer atomics only (maxima, minima and sums of integers do not
+ * depend on the order): equal inputs (the state and the layers among them) give equal bytes.  The entry computes no pose.
+ * PRECONDITION: the entry is called exactly once after every codd_local_map call on `state`, from the first one on, with the
+ * gh, gw, cell, range_min, range_max that call was given.  That is what makes "the previous origin" and CLEARED mean the same
+ * to both maps.
+ * Inputs, all DEVICE, never written: disp [H,W], the crop h, w, K = (fx, fy, cx, cy), calib, labels [h,w] and ground_record
+ * exactly as codd_local_map takes them; state: the 32 doubles as codd_local_map left them for this frame, of which [1:7]
+ * (pose and origin), [16:18] (the previous origin), [18] CLEARED and [19] INTEGRATED are read.
+ * Heights are integers in units of h_res (the unit of calib / fx), above the floor plane fitted in the frame that observed
+ * them (codd_ground_plane's height, positive upwards): not a global datum.
+ * Caller-owned, persistent, DEVICE, toroidal as logodds (world cell (ix, iz) at row iz mod gh, column ix mod gw):
+ *   top, bot int16 [gh,gw]: the highest and the lowest surface; -32768: no surface seen inside the current window;
+ *   ceil int16 [gh,gw]: the lowest overhead thing; 32767: none seen;
+ *   hage uint8 [gh,gw]: 255: never observed inside the current window; otherwise frames since the last observation,
+ *     saturating at 254.
+ *   The first codd_local_map call on a zeroed state is always CLEARED (nothing exists yet), and a CLEARED call gives every
+ *   cell its sentinels: the caller need not initialise the four layers, their contents before the first call are
+ *   irrelevant.
+ * Launch 1, enter: every cell of the new window that was not in the old one -- all of them when CLEARED; codd_local_map's
+ *   launch-2 rule on state[5:7] and [16:18] -- gets top = bot = -32768, ceil = 32767, hage = 255.  The per-frame tables (int32
+ *   [gh,gw] each, in the order of the outputs) are set: Tmax = INT_MIN, Tmin = INT_MAX, Tn = 0, Cmin = INT_MAX, Cn = 0; the
+ *   counters are zeroed.
+ * Launch 2, pixels, iff INTEGRATED.  Every operation is one fp32 operation rounded on its own (no fused multiply-add; sqrtf
+ *   and division correctly rounded).  A pixel of the crop is a SURFACE pixel iff labels[y,x] < 32 && (select >> labels[y,x])
+ *   & 1 (select must not contain the bit of CODD_GROUND_OVERHEAD; an unsigned holds no bit >= 32), an OVERHEAD pixel iff
+ *   labels[y,x] == CODD_GROUND_OVERHEAD.  Either kind needs d = disp[y,x] finite and > 0 and rho in [range_min, range_max);
+ *   rho and the cell (jz, jx) are codd_local_map's launch-3 expressions, verbatim (one header, csrc/map_window.h, holds them
+ *   for both).  hgt = ((float)Hc * e) / d with e = d - ((c0 * p0 + c1 * p1) + c2), p0 = (float)x - cx, p1 = (float)y - cy and
+ *   (c0, c1, c2, Hc) = (float) of record [0], [1], [2], [11]: the bits of codd_ground_plane's height.  A pixel whose hgt is
+ *   not finite is dropped.  q = (int)fminf(fmaxf(rintf(hgt / h_res), -32000.f), 32000.f) (rintf: ties to even).  A surface
+ *   pixel does Tmax = max(Tmax, q), Tmin = min(Tmin, q), Tn += 1 at [jz,jx]; an overhead pixel Cmin = min(Cmin, q), Cn += 1.
+ * Launch 3, update, per window cell (j, i), world cell (ix0 + i, iz0 + j), integers only, in this order, with
+ *   f(v, t) = v + (alpha * (t - v)) / 256, C's division truncating toward zero:
+ *   Tn >= min_pixels: top = (top == -32768) ? Tmax : f(top, Tmax); bot = (bot == -32768) ? Tmin : f(bot, Tmin);
+ *   Cn >= min_pixels: ceil = (ceil == 32767) ? Cmin : f(ceil, Cmin);
+ *   if either held hage = 0, otherwise hage = min(hage + 1, 254) unless it is 255.  (A frame that is not INTEGRATED has empty
+ *   tables: every cell ages and keeps its values.)  The dead band of the truncation: a target with |t - v| < 256 / alpha
+ *   moves nothing (alpha = 128: one unit), so a stored value rests within ceil(256 / alpha) - 1 units of a constant target.
+ *   f is monotone in v and in t and Tmin <= Tmax: bot <= top always.  ceil is never forgotten while the cell stays in the
+ *   window.
+ *   top_out, bot_out, ceil_out int16 [gh,gw], hage_out uint8 [gh,gw]: the unrolled layers, out[j,i] = world cell (ix0 + i,
+ *   iz0 + j), every element rewritten on every call.
+ * Launch 4, derive, on the unrolled window; neighbours are window neighbours, cells beyond the window's edge are skipped,
+ *   never wrapped.  A cell is KNOWN iff top != -32768 (a cell over which only overhead pixels were seen carries its ceil but
+ *   is not known).
+ *   step_out uint16 [gh,gw]: max(0, top - the minimum of top over the known ones of the 8 neighbours); 0 for an unknown cell
+ *   and for a cell without a known neighbour.
+ *   flags_out uint8 [gh,gw]: 255 for an unknown cell, otherwise the bit set CODD_HEIGHT_STEP (1): step > max_step_q;
+ *   CODD_HEIGHT_HEADROOM (2): ceil != 32767 && ceil - top < robot_height_q; CODD_HEIGHT_HOLE (4): bot < -max_drop_q.  Of an
+ *   edge that is too high the upper cell is the blocked one; it blocks the edge both ways.  The thresholds are integers in
+ *   units of h_res; the host quantises them once, (int)rint(v / h_res) in fp64.
+ *   record, 16 doubles, never NaN: [0] INTEGRATED, [1] surface pixels used (the sum of Tn), [2] overhead pixels used (the sum
+ *   of Cn), [3] cells observed this frame (hage 0), [4] known cells, [5:8] cells with STEP, HEADROOM, HOLE, [8] the largest
+ *   top and [9] the smallest bot over the known cells (0 without one), [10:12] ix0, iz0, [12:16] 0.  Counts are integer atomic
+ *   sums, extrema integer atomics.
+ * scratch: codd_height_map_scratch(gh, gw) bytes (-1 outside codd_local_map's limits), 20 per cell plus the counters and the
+ * alignment, contents irrelevant, any alignment.  From the first 16-byte boundary at or after the pointer it holds Tmax, Tmin,
+ * Tn, Cmin, Cn, then 16 int32 counters; after a call the tables hold the frame's values.
+ * CODD_EINVAL, before any launch (a rejected call writes no byte): any pointer NULL; a non-positive size, h > H, w > W or
+ * h w >= 2^31; gh, gw outside the limits; fx, fy, calib, cell, range_max or h_res not finite and > 0; cx or cy not finite;
+ * range_min negative, NaN or >= range_max; select with the bit of CODD_GROUND_OVERHEAD; min_pixels < 1; alpha outside [1,
+ * 256]; max_step_q, robot_height_q or max_drop_q outside [0, 32000]; scratch_bytes below the size function's answer; top,
+ * bot, ceil, top_out, bot_out, ceil_out or step_out not aligned to 2 bytes; ground_record, state or record not to 8. */
+#define CODD_HEIGHT_STEP 1
+#define CODD_HEIGHT_HEADROOM 2
+#define CODD_HEIGHT_HOLE 4
+long long codd_height_map_scratch(int gh, int gw);
+int codd_height_map(const float* disp, int H, int W, int h, int w, float fx, float fy, float cx, float cy, float calib,
+                    const unsigned char* labels, const double* ground_record, const double* state, int gh, int gw,
+                    float cell, float range_min, float range_max, float h_res, unsigned select, int min_pixels, int alpha,
+                    int max_step_q, int robot_height_q, int max_drop_q, short* top, short* bot, short* ceil,
+                    unsigned char* hage, void* scratch, long long scratch_bytes, short* top_out, short* bot_out,
+                    short* ceil_out, unsigned char* hage_out, unsigned short* step_out, unsigned char* flags_out,
+                    double* record, void* stream);
+
 /* Live-session cost map (codd_amd/live.py, costmap=): what a local planner or a safety monitor makes of the occupancy map
  * first.  Per cell of codd_local_map's unrolled window: the squared distance to the nearest occupied cell, an inflated
  * cost (so that the robot can be treated as a point), whether the robot can reach the cell from where it stands, and

@@ -49,7 +49,8 @@ def build_variant(verbose=False):
     src = os.path.join(csrc, "localmap.hip")
     out_dir = os.path.join(ROOT, "build", "live_localmap_bench")
     lib = os.path.join(out_dir, "liblocalmap_lane.so")
-    deps = [src, os.path.join(csrc, "floor_frame.h"), os.path.join(csrc, "common.h"), os.path.join(ROOT, "include", "codd_hip.h")]
+    deps = [src, os.path.join(csrc, "map_window.h"), os.path.join(csrc, "floor_frame.h"), os.path.join(csrc, "common.h"),
+            os.path.join(ROOT, "include", "codd_hip.h")]
     if os.path.exists(lib) and os.path.getmtime(lib) >= max(os.path.getmtime(d) for d in deps):
         return lib
     os.makedirs(out_dir, exist_ok=True)
